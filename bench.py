@@ -31,8 +31,17 @@ in which the plan launches eagerly with HIP events around every launch of that k
 stream (the kernels are identical); rocprofv3's average for the same command, committed under
 profiles/, is reported beside it (`*_rocprof`).
 
-Output: the LAST stdout line on rank 0 is ONE compact JSON headline (<= 2 KB, `headline_line`)
-with `roofline` and, at N=1, `cpu_baseline` (the oracle's numpy pairwise executor on a bounded
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it
+builds the plan, warms up, times the K steps and prints the result line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the workload's `config`).  `--dump-outputs DIR` also
+writes what the last timed step computed -- the block of amplitudes a caller of that step receives
+-- as DIR/amplitudes.npy (float32, the complex64 values as a trailing [re, im] axis); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
+Everything else below (the latency and profiled passes, `roofline`, the permute probe, the CPU
+baseline, the other configs and GEMM kernels, the C5 line, `slices_strong`) runs only with `--full`.
+
+Output: the LAST stdout line on rank 0 is ONE compact JSON headline (<= 2 KB, `headline_line`);
+with `--full` it holds `roofline` and, at N=1, `cpu_baseline` (the oracle's numpy pairwise executor on a bounded
 sample of the same network, in the same dtype) and one [value, ms, frac] triple per secondary
 line; the secondary sections in full go to stderr (`[bench-detail]` lines) and, with `--details
 PATH`, to a JSON file.
@@ -323,7 +332,7 @@ def alt_gemm(args, envs: dict, desc: str, cfg: str):
     import subprocess
     env = dict(os.environ, **envs)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-c5", "--no-alt", "--no-other"]
+           "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-c5", "--no-alt", "--no-other"]
     d = _child_details(cmd, env)
     return {"config": cfg, "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"],
             "gemm": f"{desc} ({' '.join(f'{k}={v}' for k, v in envs.items())})", "roofline": d["roofline"]}
@@ -335,7 +344,7 @@ def other_config(args, cfg: str):
     builds its own plan and arena); the headline stays C4."""
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--no-c5", "--no-alt", "--no-other",
+           "--warmup", str(args.warmup), "--full", "--no-c5", "--no-alt", "--no-other",
            "--cpu-seconds", str(args.other_cpu_seconds)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
@@ -395,6 +404,13 @@ def main():
     ap.add_argument("--batch", type=int, default=0,
                     help="bitstring sharding: rank r contracts block batch + r (tests: a 1-rank run of "
                          "another rank's block)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the amplitudes the LAST timed step computed to DIR/amplitudes.npy "
+                         "(float32, trailing axis [re, im])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else: the latency and profiled passes "
+                         "(roofline), the permute probe, the CPU baseline, the other configs and GEMM kernels, "
+                         "the C5 training line, slices_strong at N > 1 (the --no-* switches trim these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 training-step line")
     ap.add_argument("--no-alt", action="store_true",
@@ -504,9 +520,10 @@ def main():
         else:
             expr(*ops, out=out)
 
+    last_step = [None]   # the output tensor of the most recent pipelined step (--dump-outputs)
     if bitstrings:
         def step():
-            pipe.step()
+            last_step[0] = pipe.step()
 
         def last_out():
             # block batch + r again on slot 0 (the saved block is deterministic per rank)
@@ -548,6 +565,15 @@ def main():
     # ---- headline: production path (hipGraph replay per step, no events)
     dt = max_over_ranks(timed(args.steps))
     graphs = plan.query("graph_launches")
+    if args.dump_outputs:
+        # the last timed step's own output buffer, read before any later pass runs on its slot
+        # (slice sharding: every rank waits for its pending reduces; rank 0 writes)
+        o = last_step[0] if bitstrings else last_out()
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        o = np.ascontiguousarray(o.cpu().numpy())
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "amplitudes.npy"), o.view(np.float32).reshape(o.shape + (2,)))
     if args.save_out:
         res = last_out()
         import numpy as np
@@ -557,7 +583,7 @@ def main():
             root, ext = os.path.splitext(args.save_out)
             np.save(f"{root}.rank{rank}{ext}", res.cpu().numpy())
     slices_strong = None
-    if bitstrings and world > 1:
+    if args.full and bitstrings and world > 1:
         # the same ranks on ONE block, its slices sharded + the RCCL all-reduce (strong scaling)
         s_step, s_last = slices_job()
         for _ in range(args.warmup):
@@ -576,6 +602,49 @@ def main():
         _log(f"slices (strong) on one block: {dts / args.steps * 1e3:.2f} ms/step")
 
     _log(f"headline: {dt / args.steps * 1e3:.2f} ms/step ({inflight} groups of {group} in flight)")
+    n_amp = task.n_amplitudes * (world if bitstrings else 1)   # amplitudes of the whole job per step
+    value = n_amp * args.steps / dt
+    head = {
+        "metric": "amplitudes/sec + achieved MFMA TFLOP/s, 53q depth-20 RQC",
+        "value": value,
+        "unit": "amplitudes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak" if args.shard == "bitstrings" else "strong",
+        "vs_baseline": None,
+        "dtype": "c64",
+        "data": "synthetic (Haar-random 2-qubit cores, seeded; |0> inputs; seeded fixed bits)",
+        "config": {
+            "workload": (f"{args.config}: {task.circuit.n_qubits}q depth-{task.circuit.depth} brick-wall RQC, "
+                         f"{task.n_amplitudes} correlated amplitudes per block ({len(task.open_qubits)} open), "
+                         f"cut {task.cut}, {n_slices} slices ({len(task.sliced)} sliced cut legs); "
+                         + (f"{world} GPU(s), one block per rank (bitstring sharding, no collective)" if bitstrings
+                            else f"{world} GPU(s), slices sharded, RCCL all-reduce")),
+            "n_qubits": task.circuit.n_qubits,
+            "depth": task.circuit.depth,
+            "amplitudes_per_step": n_amp,
+            "amplitudes_per_block": task.n_amplitudes,
+            "blocks_per_step": world if bitstrings else 1,
+            "slices": n_slices,
+            "parallelism": f"bitstrings{world}" if bitstrings else f"slices{world}",
+            "slices_per_rank": n_slices if bitstrings else len(range(rank, n_slices, world)),
+        },
+    }
+    headline_how = ("hipGraph replay of the whole plan per step (production path), no events"
+                    + (f"; {group} blocks per lockstep group (blocks as lanes), {inflight} groups in flight "
+                       f"per GPU on their own streams (each step one whole block)" if inflight * group > 1 else ""))
+    if not args.full:
+        # a plain run ends here: the headline alone
+        res = dict(head, timing={"headline": headline_how, "graph_launches_timed": graphs, "inflight": inflight,
+                                 "group": group}, plan={"compile_s": t_plan})
+        if rank == 0:
+            emit(res, args.details or os.environ.get("TQ_BENCH_DETAILS"))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # ---- one block at a time (one stream): the latency of a step
     dt_lat = max_over_ranks(timed(args.steps, step1)) if inflight * group > 1 else dt
     # ---- dominant kernel: the same K steps launched eagerly (one stream) with HIP events around
@@ -592,14 +661,12 @@ def main():
     kinds = {k: plan.profile_read(getattr(_lib, f"TQ_OP_{k}")) for k in ("APPLY", "SWEEP", "PERMUTE", "GEMM")}
     plan.profile(None)
 
-    n_amp = task.n_amplitudes * (world if bitstrings else 1)   # amplitudes of the whole job per step
     L = _lib.lib()
     g3m = bool(L.tq_library_query(b"gemm_3m") == 1)
     bf16 = bool(L.tq_library_query(b"gemm_bf16") == 1)
     f16 = bf16 and bool(L.tq_library_query(b"gemm_f16") == 1)
     f16_g3 = f16 and L.tq_library_query(b"gemm_f16_var") in (2, 5, 6, 7, 8, 9)   # Gauss 3M on the f16 terms
     planes = plan.query("planes_active") == 1   # the pre-split boundary GEMM (tq_gemmp.hip)
-    value = n_amp * args.steps / dt
     nl = max(1, gemm["launches"])
     avg_gemm_s = gemm["ms"] / 1e3 / nl
     alg_flops = gemm["flops"] / nl                      # 8*M*N*K complex GEMM flops per launch
@@ -664,37 +731,9 @@ def main():
     sweep_ = kinds["SWEEP"]
     perm_ = kinds["PERMUTE"]
     res = {
-        "metric": "amplitudes/sec + achieved MFMA TFLOP/s, 53q depth-20 RQC",
-        "value": value,
-        "unit": "amplitudes/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak" if args.shard == "bitstrings" else "strong",
-        "vs_baseline": None,
-        "dtype": "c64",
-        "data": "synthetic (Haar-random 2-qubit cores, seeded; |0> inputs; seeded fixed bits)",
-        "config": {
-            "workload": (f"{args.config}: {task.circuit.n_qubits}q depth-{task.circuit.depth} brick-wall RQC, "
-                         f"{task.n_amplitudes} correlated amplitudes per block ({len(task.open_qubits)} open), "
-                         f"cut {task.cut}, {n_slices} slices ({len(task.sliced)} sliced cut legs); "
-                         + (f"{world} GPU(s), one block per rank (bitstring sharding, no collective)" if bitstrings
-                            else f"{world} GPU(s), slices sharded, RCCL all-reduce")),
-            "n_qubits": task.circuit.n_qubits,
-            "depth": task.circuit.depth,
-            "amplitudes_per_step": n_amp,
-            "amplitudes_per_block": task.n_amplitudes,
-            "blocks_per_step": world if bitstrings else 1,
-            "slices": n_slices,
-            "parallelism": f"bitstrings{world}" if bitstrings else f"slices{world}",
-            "slices_per_rank": n_slices if bitstrings else len(range(rank, n_slices, world)),
-        },
+        **head,
         "timing": {
-            "headline": ("hipGraph replay of the whole plan per step (production path), no events"
-                         + (f"; {group} blocks per lockstep group (blocks as lanes), {inflight} groups in flight "
-                            f"per GPU on their own streams (each step one whole block)" if inflight * group > 1 else "")),
+            "headline": headline_how,
             "graph_launches_timed": graphs,
             "eager_profiled_ms_per_step": dt_prof / args.steps * 1e3,
             "inflight": inflight,
@@ -919,7 +958,8 @@ def headline(res: dict) -> dict:
     for k in ("traffic_source", "rocprof_source"):
         if k in rf:
             r[k] = _short(rf[k], 60)
-    h["roofline"] = r
+    if rf:   # (a plain run has none)
+        h["roofline"] = r
     if res.get("roofline_gemm"):
         h["roofline_gemm"] = _rounded(_pick(res["roofline_gemm"], ("achieved", "peak", "unit", "frac")))
     cb = res.get("cpu_baseline")

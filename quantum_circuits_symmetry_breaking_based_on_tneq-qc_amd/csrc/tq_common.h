@@ -138,6 +138,8 @@ bool gemm_presplit_enabled();
 // per slice, before the producers: sc[i] = scale for the next operand from the previous max
 // (amax[i]; 0 = none yet), amax[i] = 0
 int presplit_prep_launch(uint32_t* amax, int32_t* sc, int n, hipStream_t stream);
+// w[0 .. n) = 0 by a kernel (the operand max words before their producers run)
+int zero_words_launch(uint32_t* w, int n, hipStream_t stream);
 // amax_a / amax_b (optional, complex64): float bits of max |re|, |im| over A / B, written by the
 // operands' producers (plan: the sweep ops that store them); the f16-split kernel then skips its
 // own max pre-pass over A and B.  amax_bs_a / amax_bs_b: word stride between batch entries (0: one

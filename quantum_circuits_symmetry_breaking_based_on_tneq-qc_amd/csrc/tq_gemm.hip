@@ -861,6 +861,10 @@ __global__ void presplit_prep_kernel(uint32_t* amax, int32_t* sc, int n, int bia
   }
 }
 
+__global__ void zero_words_kernel(uint32_t* w, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) w[i] = 0;
+}
+
 template <int N>
 __device__ __forceinline__ void st_lds(char* p, const uint32_t (&w)[N / 2]) {
   if constexpr (N == 8) *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -1967,6 +1971,13 @@ bool gemm_c64_presplit_ok(int transA, int transB, int64_t M, int64_t N, int64_t 
          fast_c64_splits_t<xbf::TileX>(transA, transB, M, N, K, batch) > 0;
 }
 
+int zero_words_launch(uint32_t* w, int n, hipStream_t stream) {
+  if (n <= 0) return TQ_OK;
+  hipLaunchKernelGGL(xbf::zero_words_kernel, dim3(1), dim3(64), 0, stream, w, n);
+  TQ_HIP(hipGetLastError());
+  return TQ_OK;
+}
+
 int presplit_prep_launch(uint32_t* amax, int32_t* sc, int n, hipStream_t stream) {
   if (n <= 0) return TQ_OK;
   hipLaunchKernelGGL(xbf::presplit_prep_kernel, dim3(1), dim3(64), 0, stream, amax, sc, n, presplit_bias());
@@ -2309,7 +2320,8 @@ int launch_typed(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_
           } else {
             // one max per batch entry and operand: every entry scaled by its own max
             uint32_t* amax = reinterpret_cast<uint32_t*>(static_cast<char*>(W) + slab);
-            TQ_HIP(hipMemsetAsync(amax, 0, 2 * batch * sizeof(uint32_t), stream));
+            // (a kernel, not hipMemsetAsync: see Exec::run on memset nodes of a captured graph)
+            TQ_TRY(zero_words_launch(amax, (int)(2 * batch), stream));
             const int64_t per = std::max<int64_t>(1, 1024 / batch);
             const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((K + 3) / 4, per));
             hipLaunchKernelGGL(xbf::absmax_kouter_kernel, dim3(gx, 2, (unsigned)batch), dim3(256), 0, stream,

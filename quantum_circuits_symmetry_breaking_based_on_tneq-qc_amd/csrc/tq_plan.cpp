@@ -3806,8 +3806,15 @@ int Exec::run(int64_t s_begin, int64_t s_end, int64_t s_step, int accumulate) {
     }
     const int nl = (int)I_[0].lane_sl.size();
     if (s0 == s_begin) {
-      for (auto& x : I_)
-        if (x.P->n_amax_once) TQ_HIP(hipMemsetAsync(amax_word(x, 0), 0, x.P->n_amax_once * sizeof(uint32_t), st_));
+      // max words are zeroed by a kernel, not hipMemsetAsync: with the zeroing as a memset node
+      // of the plan's captured graph, replays left the f16-split GEMM a max of 0 or one too small
+      // (all-zero / all-NaN outputs; mis-ordered node or carried-over max: DESIGN.md §5)
+      // one launch for the hoisted part's words and (not pre-split) the first batch's per-slice
+      // words behind them
+      for (auto& x : I_) {
+        const int n = x.P->n_amax_once + (x.P->run_mode ? 0 : x.P->n_amax_slice * nl);
+        TQ_TRY(zero_words_launch(amax_word(x, 0), n, st_));
+      }
       size_t run = 0, crun = 0;
       for (int i = 0; i < (int)P0_.sched_once.size();) {
         while (P0_.use_seq && run < P0_.seq_once.size() && P0_.seq_once[run].first < i) ++run;
@@ -3832,8 +3839,8 @@ int Exec::run(int64_t s_begin, int64_t s_end, int64_t s_step, int accumulate) {
       const Plan& P = *x.P;
       if (P.n_amax_slice && P.run_mode)   // scales from the previous slice's max, then max = 0
         TQ_TRY(presplit_prep_launch(amax_word(x, P.n_amax_once), sc_word(x, P.n_amax_once), P.n_amax_slice, st_));
-      else if (P.n_amax_slice)
-        TQ_HIP(hipMemsetAsync(amax_word(x, P.n_amax_once), 0, (size_t)P.n_amax_slice * nl * sizeof(uint32_t), st_));
+      else if (P.n_amax_slice && s0 != s_begin)   // (the first batch's: zeroed above)
+        TQ_TRY(zero_words_launch(amax_word(x, P.n_amax_once), P.n_amax_slice * nl, st_));
     }
     for (auto& grp : P0_.sched_slice) {
       const Op& op0 = P0_.ops[grp[0]];

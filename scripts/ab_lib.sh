@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
-B="python3 bench.py --no-cpu-baseline --no-c5 --no-alt --no-other"
+B="python3 bench.py --full --no-cpu-baseline --no-c5 --no-alt --no-other"
 libenv() { [ -n "$1" ] && echo "TNEQHIP_LIB=$PWD/$1"; }
 for spec in "$@"; do
   l=${spec%%:*}; p=${spec#*:}

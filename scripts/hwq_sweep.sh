@@ -9,7 +9,7 @@ for spec in "$@"; do
   g=${g:-1}
   label="q${q}_i${i}_g${g}"
   echo "== $label"
-  GPU_MAX_HW_QUEUES=$q timeout -k 10 200 python3 bench.py --config ${CFG:-C4} --no-cpu-baseline --no-c5 --no-alt \
+  GPU_MAX_HW_QUEUES=$q timeout -k 10 200 python3 bench.py --config ${CFG:-C4} --full --no-cpu-baseline --no-c5 --no-alt \
     --no-other --steps ${STEPS:-40} --inflight "$i" --group "$g" > gpurun_out/hwq_$label.log 2>&1 || exit 1
   python3 -c "
 import json

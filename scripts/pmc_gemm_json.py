@@ -6,7 +6,7 @@ XCDs / kernel duration), and HBM bytes per launch (FETCH_SIZE doubled per the gf
 in MI355X_MICROARCH.md's HBM section, + WRITE_SIZE)."""
 import collections, csv, json, sys
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out"
+root = sys.argv[1] if len(sys.argv) > 1 else "prof_out"
 out = sys.argv[2] if len(sys.argv) > 2 else "profiles/pmc_gemm_bf16_r02.json"
 kind = sys.argv[3] if len(sys.argv) > 3 else "bf16"
 # slices per launch (the plan's slice lanes: one batched launch per batch) and split-K count
@@ -47,7 +47,7 @@ res = {
                "gemm_c64_kouter_split_kernel<TileX, SplitBF16> (complex64 via exact 3-term bf16 split, 4M, ")
               + f"M=N=1024, K=65536 per slice, block 128x128, batch {batch} (slice lanes), split-K {splits})",
     "command": f"scripts/pmc_gemm_{kind}.sh (rocprofv3 --pmc ... --kernel-include-regex gemm_c64 -- python3 bench.py "
-               "--no-cpu-baseline --no-c5 --steps 2 --warmup 1; FETCH_SIZE and WRITE_SIZE in separate passes; "
+               "--full --no-cpu-baseline --no-c5 --steps 2 --warmup 1; FETCH_SIZE and WRITE_SIZE in separate passes; "
                "durations from a --kernel-trace pass)",
     "launches": n1,
     "counters_avg_per_launch": c1,

@@ -6,7 +6,7 @@ TAG=${1:-r05}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out/t$TAG
 O=gpurun_out/t$TAG
 for cfg in ${CFGS:-C2 C3 C4 C4x4}; do
-  B="python3 bench.py --config $cfg --no-cpu-baseline --no-c5 --no-alt --no-other --steps 2 --warmup 1"
+  B="python3 bench.py --config $cfg --full --no-cpu-baseline --no-c5 --no-alt --no-other --steps 2 --warmup 1"
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 90 rocprofv3 --pmc $c --kernel-include-regex sweep --output-format csv -d $O/${cfg}_$c -o run -- $B > $O/${cfg}_$c.log 2>&1 || exit 1
   done

@@ -33,7 +33,7 @@ for cfg in ("C2", "C3", "C4", "C4x4"):
         continue
     d = {"config": cfg,
          "command": f"rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --kernel-include-regex sweep -- "
-                    f"python3 bench.py --config {cfg} --no-cpu-baseline --no-c5 --no-alt --no-other --steps 2 --warmup 1",
+                    f"python3 bench.py --config {cfg} --full --no-cpu-baseline --no-c5 --no-alt --no-other --steps 2 --warmup 1",
          "definition": "sweep_hbm_bytes = sum over the sweep dispatches of (2*FETCH_SIZE + WRITE_SIZE) * 1024",
          "sweep_dispatches": fd, "write_dispatches": wd, "sweep_hbm_bytes": (2 * fk + wk) * 1024,
          "fetch_kB_total": fk, "write_kB_total": wk}

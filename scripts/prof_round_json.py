@@ -46,7 +46,7 @@ trace = dispatches(f"{root}/k0/run_kernel_trace.csv", value_col=False)
 passes = [dispatches(f"{root}/p{i}/run_counter_collection.csv") for i in (1, 2, 3, 4)]
 res = {"config": "C4",
        "command": f"scripts/prof_round.sh {TAG}: rocprofv3 --pmc <set> --kernel-include-regex "
-                  "'split_kernel|gemm_planes_kernel|sweepd_kernel|sweep2_kernel' -- python3 bench.py --no-cpu-baseline --no-c5 "
+                  "'split_kernel|gemm_planes_kernel|sweepd_kernel|sweep2_kernel' -- python3 bench.py --full --no-cpu-baseline --no-c5 "
                   "--no-alt --steps 2 --warmup 1 (4 counter passes + a kernel-trace pass of the same command)",
        "definitions": {
            "hbm_bytes": "2*FETCH_SIZE + WRITE_SIZE (kB x 1024; gfx950 FETCH_SIZE correction)",

@@ -68,6 +68,18 @@ def test_emit_last_stdout_line_is_the_headline(tmp_path):
     assert json.loads(path.read_text())["config_C4x4"] == res["config_C4x4"]
 
 
+def test_headline_of_a_plain_run():
+    """A run without --full has the contract keys, `config`, `timing` and `plan` only."""
+    full = _full()
+    res = {k: full[k] for k in REQUIRED[:13]}
+    res["timing"] = {"headline": full["timing"]["headline"], "graph_launches_timed": 50, "inflight": 4, "group": 1}
+    res["plan"] = {"compile_s": 1.3}
+    h = json.loads(bench.headline_line(res))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert h[k] == full[k], k
+    assert not {"roofline", "roofline_gemm", "cpu_baseline", "secondary"} & set(h)
+
+
 @pytest.mark.parametrize("key", ["roofline", "cpu_baseline"])
 def test_headline_survives_missing_sections(key):
     res = _full()

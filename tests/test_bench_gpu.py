@@ -5,6 +5,9 @@ MASTER_ADDR), here all on cuda:0 over gloo (RCCL needs one GPU per rank).
 * bitstring sharding (the default): rank r's block equals a 1-rank run of block r (`--batch r`),
   and the strong-scaling pass on block 0 (slices sharded + all-reduce) equals the 1-rank block 0;
 * `--shard slices`: the reduced amplitudes equal the 1-rank run's.
+
+These runs pass `--full` (they check `roofline` and `slices_strong`); a plain run prints the
+headline alone and `--dump-outputs` writes the last timed step's amplitudes.
 """
 import json
 import os
@@ -17,7 +20,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--config", "C4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-c5", "--no-alt", "--no-other"]
+COMMON = ["--config", "C4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-c5", "--no-alt",
+          "--no-other"]
 
 
 def _run(args, out):
@@ -78,3 +82,29 @@ def test_bench_eight_ranks_one_slice_each(tmp_path):
     _close(a, np.load(tmp_path / "eight.npy"))
     _close(a, np.load(tmp_path / "eight.slices.npy"))
     _close(np.load(tmp_path / "one_b7.npy"), np.load(tmp_path / "eight.rank7.npy"))
+
+
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A plain run (no --full): the result line holds the headline keys and none of the sections
+    that take passes of their own; `--dump-outputs` writes the block the LAST timed step
+    contracted.  64 + 1 steps walk the 64-block window once round, so that block is block 0 again,
+    the one `--save-out` recomputes after the timed steps."""
+    d, out = tmp_path / "dump", str(tmp_path / "b0.npy")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "63", "--warmup", "2",
+                        "--dump-outputs", str(d), "--save-out", out],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    h = json.loads(lines[0])
+    assert h["metric"].startswith("amplitudes/sec") and h["unit"] == "amplitudes/s" and h["dtype"] == "c64"
+    assert h["higher_is_better"] is True and h["steps"] == 63 and h["warmup"] == 2
+    assert h["ms_per_step"] > 0
+    assert h["value"] == pytest.approx(h["config"]["amplitudes_per_step"] / (h["ms_per_step"] * 1e-3), rel=1e-3)
+    for k in ("roofline", "cpu_baseline", "secondary", "hbm_kernels"):
+        assert k not in h, k
+    assert os.listdir(d) == ["amplitudes.npy"]
+    a = np.load(d / "amplitudes.npy")
+    assert a.dtype == np.float32 and a.shape == (2,) * 20 + (2,) and a.nbytes <= 64 * 2 ** 20
+    assert np.isfinite(a).all()
+    _close(np.load(out), a[..., 0] + 1j * a[..., 1])

@@ -53,6 +53,36 @@ def test_pipelined_c4_blocks_equal_single_runs(dev, inflight, group):
     assert not np.allclose(got[0], got[1])   # other blocks, other amplitudes
 
 
+def test_replayed_c4_blocks_one_at_a_time(dev):
+    """Graph replays on an idle GPU: one C4 block at a time with a synchronize after each (the plan's
+    graph is captured on block 0 and replayed for the rest).  The operand max words of the f16-split
+    boundary GEMM were zeroed by a captured memset node that a replay did not keep in order with
+    the words' producers: blocks 5-7 came back all zero and 8-11 all NaN.  Every block is finite
+    and non-zero, and blocks 5 and 8 equal an eagerly launched plan's result (no graph)."""
+    import torch
+    from tneq_qc_amd.circuits import config_task, with_batch
+    from tneq_qc_amd.expression import HipContractExpression
+    from tneq_qc_amd.sampling import BlockPipeline
+    t = config_task("C4")
+    pipe = BlockPipeline(t, list(range(12)), inflight=1, device=dev)
+    got = []
+    for _ in range(12):
+        o = pipe.step()
+        pipe.synchronize()
+        got.append(o.cpu().numpy().copy())
+    for b, g in enumerate(got):
+        assert np.isfinite(g).all() and np.abs(g).max() > 0, b
+    # the reference launches eagerly: its plan captures and replays no graph
+    e = HipContractExpression(t.eq, *t.shapes, optimize=t.path, slices=t.sliced)
+    eager = e.plan(torch.complex64, None, dev.index)
+    eager.set("graph", 0)
+    for b in (5, 8):
+        tb = with_batch(t, b)
+        ref = e(*[torch.from_numpy(x).to(dev, torch.complex64) for x in tb.operands]).cpu().numpy()
+        assert np.abs(got[b] - ref).max() <= 1e-5 * np.abs(ref).max(), b
+    assert eager.query("graph_builds") == 0 and eager.query("graph_launches") == 0
+
+
 def test_run_group_refuses_mismatched_members(dev):
     import torch
     from tneq_qc_amd.expression import HipContractExpression, run_group
