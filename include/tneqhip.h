@@ -172,7 +172,11 @@ int tq_plan_clone(tq_plan src, tq_plan* out);
  * (the plan is compiled again): "group_hint" = G compiles for lockstep groups of G plans
  * (tq_plan_execute_group: every sweep op shares its launches, so ops take G x fewer, wider
  * chunks); "min_chunks" = n > 0 splits every big sweep op into at least n chunks (default 128,
- * env TQ_S2_MINCHUNKS; a caller with several plans in flight on other streams wants fewer). */
+ * env TQ_S2_MINCHUNKS; a caller with several plans in flight on other streams wants fewer);
+ * "s2_programs" = 1 (default, env TQ_S2_PROG) runs the sweep2 register-block passes whose gate
+ * sequence is in the kernel's program set as straight-line pass programs, 0 all of them on the
+ * per-gate interpreter (no recompile; queries "n_s2_prog_gate_work" / "n_s2_block_gate_work":
+ * gate work under programs / of all block passes, "n_s2_prog_passes_<id>", "n_s2_programs"). */
 int tq_plan_set(tq_plan plan, const char* key, int64_t value);
 /* human-readable per-step description into buf (for debugging / DESIGN evidence) */
 int tq_plan_describe(tq_plan plan, char* buf, size_t n);

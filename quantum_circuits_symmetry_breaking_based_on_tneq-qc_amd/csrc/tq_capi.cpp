@@ -1,4 +1,5 @@
 // extern "C" surface of libtneqhip.so (declared in include/tneqhip.h).
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <exception>
@@ -8,6 +9,7 @@
 #include "tq_common.h"
 #include "tq_optim.h"
 #include "tq_plan.h"
+#include "tq_sweep2.h"
 
 // development aid: TQ_TRACE_FILE=<path> appends a line per plan execute / destroy step (finds
 // which call a native abort comes from when the test runner swallows stderr)
@@ -303,6 +305,14 @@ int tq_plan_set(tq_plan p, const char* key, int64_t value) {
     p->plan.use_coop = value != 0;
     return TQ_OK;
   }
+  if (k == "s2_programs") {      // 0: every sweep2 register-block pass on the interpreter
+    if (p->materialized) {
+      tq::set_error("tq_plan_set: s2_programs before the plan's first execute only");
+      return TQ_ERR_INVALID;
+    }
+    tq::plan_s2_programs(p->plan, value != 0);
+    return TQ_OK;
+  }
   tq::set_error("tq_plan_set: unknown key " + k);
   return TQ_ERR_INVALID;
 }
@@ -372,6 +382,11 @@ int64_t tq_plan_query(tq_plan p, const char* key) {
     if (k == "planes_gemm_lda") return g.lda;
     if (k == "planes_gemm_ldb") return g.ldb;
   }
+  if (k == "s2_programs") return P.use_s2_prog ? 1 : 0;
+  if (k == "n_s2_programs") return tq::kS2NumProgs;   // program ids are 1 .. n_s2_programs
+  if (k.rfind("n_s2_prog_passes_", 0) == 0) return tq::plan_s2_prog_passes(P, atoi(k.c_str() + 17));
+  if (k == "n_s2_block_gate_work") return tq::plan_s2_gate_work(P, false);
+  if (k == "n_s2_prog_gate_work") return tq::plan_s2_gate_work(P, true);
   if (k == "out_numel") return P.out_numel;
   return -1;
 }

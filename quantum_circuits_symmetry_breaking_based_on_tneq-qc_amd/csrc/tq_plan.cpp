@@ -2882,7 +2882,81 @@ int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, cons
   a.sliced.assign(sliced_modes, sliced_modes + n_sliced);
   P.group_hint = group_hint;
   P.min_chunks = min_chunks;
+  static const bool prog_default = [] {   // TQ_S2_PROG=0: every block pass on the interpreter
+    const char* e = getenv("TQ_S2_PROG");
+    return !(e && e[0] == '0');
+  }();
+  plan_s2_programs(P, prog_default);
   return TQ_OK;
+}
+
+namespace {
+// every descriptor of the plan's (non-dense) sweep2 ops: fn(op, descriptor, is the op's default layout)
+template <typename PlanT, typename F>
+void for_s2_descs(PlanT& P, F fn) {
+  for (auto& op : P.ops) {
+    if (op.kind != OP_SWEEP2 || op.s2_dense || op.stab < 0) continue;
+    using D = typename std::conditional<std::is_const<PlanT>::value, const S2Desc, S2Desc>::type;
+    fn(op, *reinterpret_cast<D*>(P.stabs[op.stab].data()), true);
+    if (op.stab1 >= 0 && op.stab1 != op.stab) fn(op, *reinterpret_cast<D*>(P.stabs[op.stab1].data()), false);
+  }
+}
+bool s2_plain_block(const int32_t* pm) {
+  return (pm[kS2PmB] & 0xff) != 0 && !(pm[kS2PmB] & kS2PmLanes);
+}
+}  // namespace
+
+void plan_s2_programs(Plan& P, bool on) {
+  P.use_s2_prog = on;
+  for_s2_descs(P, [&](Op&, S2Desc& d, bool) {
+    for (int p = 0; p < d.npass; ++p) {
+      int32_t* pm = d.k.pmeta[p];
+      if (!s2_plain_block(pm)) continue;
+      const int B = pm[kS2PmB] & 0xff;
+      pm[kS2PmB] = B | (on ? s2_prog_bits(B, pm + kS2PmCode, pm[kS2PmCount] & 0xff) : 0);
+    }
+  });
+}
+
+int64_t plan_s2_prog_passes(const Plan& P, int id) {
+  int64_t n = 0;
+  for_s2_descs(P, [&](const Op&, const S2Desc& d, bool) {
+    for (int p = 0; p < d.npass; ++p)
+      n += s2_plain_block(d.k.pmeta[p]) && ((d.k.pmeta[p][kS2PmB] >> kS2ProgShift) & 0xff) == id;
+  });
+  return n;
+}
+
+int64_t plan_s2_gate_work(const Plan& P, bool programs_only) {
+  double w = 0;
+  std::map<std::string, double> hist;
+  const bool dump = getenv("TQ_S2_DUMP") != nullptr && !programs_only;
+  for_s2_descs(P, [&](const Op& op, const S2Desc& d, bool dflt) {
+    if (!dflt) return;
+    for (int p = 0; p < d.npass; ++p) {
+      const int32_t* pm = d.k.pmeta[p];
+      if (!s2_plain_block(pm)) continue;
+      const int B = pm[kS2PmB] & 0xff, cnt = pm[kS2PmCount] & 0xff;
+      const double elems = (double)((int64_t(1) << d.logC) << (__builtin_popcount((uint32_t)pm[kS2PmPass]) + B));
+      const double pw = cnt * elems * (double)d.nchunks * (op.invariant ? 1 : P.lanes);
+      if (!programs_only || ((pm[kS2PmB] >> kS2ProgShift) & 0xff)) w += pw;
+      if (dump) {
+        std::string key = "B" + std::to_string(B) + " id" + std::to_string((pm[kS2PmB] >> kS2ProgShift) & 0xff) + ":";
+        for (int q = 0; q < cnt; ++q) {
+          const int c = pm[kS2PmCode + q];
+          key += " " + std::to_string(c & 3) + ((c & 16) ? std::to_string((c >> 2) & 3) : std::string());
+        }
+        hist[key] += pw;
+      }
+    }
+  });
+  if (dump) {
+    std::vector<std::pair<double, std::string>> v;
+    for (auto& h : hist) v.push_back({h.second, h.first});
+    std::sort(v.rbegin(), v.rend());
+    for (auto& h : v) fprintf(stderr, "s2 block gate work %.4f  %s\n", w > 0 ? h.first / w : 0.0, h.second.c_str());
+  }
+  return (int64_t)w;
 }
 
 int plan_recompile(Plan& P, int group_hint, int min_chunks) {
@@ -2891,6 +2965,7 @@ int plan_recompile(Plan& P, int group_hint, int min_chunks) {
   if (group_hint == P.group_hint && min_chunks == P.min_chunks) return TQ_OK;
   const CompileArgs a = P.args;
   const bool seq = P.use_seq, coop = P.use_coop, planes = P.use_planes, graph = P.use_graph;
+  const bool prog = P.use_s2_prog;
   Plan Q;
   TQ_TRY(plan_compile(Q, P.dtype, (int)a.in_ranks.size(), a.in_ranks.data(), a.in_modes.data(),
                       a.in_extents.data(), a.in_strides.empty() ? nullptr : a.in_strides.data(),
@@ -2900,6 +2975,7 @@ int plan_recompile(Plan& P, int group_hint, int min_chunks) {
   Q.use_coop = coop;
   Q.use_planes = planes;
   Q.use_graph = graph;
+  plan_s2_programs(Q, prog);
   P = std::move(Q);
   return TQ_OK;
 }

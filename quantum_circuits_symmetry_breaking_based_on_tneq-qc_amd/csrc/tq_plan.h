@@ -206,6 +206,9 @@ struct Plan {
   std::vector<int> coop_width;
   size_t sync_off = 0;
   bool use_coop = false;     // TQ_S2_COOP (default off) / tq_plan_set "sweep_coop"
+  // pass programs of the sweep2 block passes (tq_sweep2.h kS2Progs): env TQ_S2_PROG, default 1;
+  // tq_plan_set "s2_programs" (plan_s2_programs, before the first execute)
+  bool use_s2_prog = true;
   std::string describe;
   // hipGraph of the whole launch sequence of one execute call, replayed while the call's
   // pointers / slice range / flags are unchanged (a plan is hundreds of small launches)
@@ -251,6 +254,14 @@ int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, cons
 // compile the plan again for lockstep groups of `group_hint` plans and with `min_chunks` (0:
 // the default) chunks per big sweep op at least (before its first execute)
 int plan_recompile(Plan& P, int group_hint, int min_chunks);
+// write (on) or clear (off) the program ids of every plain register-block pass in the plan's
+// sweep2 descriptors (host copies: before the tables are uploaded)
+void plan_s2_programs(Plan& P, bool on);
+// gate applications x chunk elements x chunks (x lanes for per-slice ops) over the register-block
+// passes of the plan's sweep2 ops; programs_only: the passes that run a pass program
+int64_t plan_s2_gate_work(const Plan& P, bool programs_only);
+// register-block passes (of every sweep2 descriptor, one-chunk forms included) that run program id
+int64_t plan_s2_prog_passes(const Plan& P, int id);
 // a copy of a compiled plan without any device state (arena, tables, graphs, events): the
 // same schedule for another stream / block (tq_plan_clone)
 void plan_clone_compiled(const Plan& src, Plan& dst);

@@ -126,6 +126,65 @@ constexpr int kS2SwapCode = 32;        // block code flag: swap a register bit w
 static_assert(sizeof(S2Keep::pmeta[0]) == kS2PmWords * sizeof(int32_t), "pass row words");
 constexpr int kS2PmSync = 1 << 16;   // count-word flag: a workgroup barrier before this pass
 constexpr int kS2BlkMaxGates = 8;      // gates per register block
+// Pass programs: a plain register block whose block-local gate codes match one of these lists is
+// run by straight-line code (tq_sweep2.hip block_pass<T, B, ID>) instead of the per-gate
+// interpreter.  The pass's B word carries the program id (1 + index here; 0 = interpreter) in
+// bits [16, 24) and, two bits per program step in bits [24, 32), which gate of the pass (offset
+// from its first) each step applies: gates on disjoint block bits commute (as s2_reorder_squares
+// relies on: the same products, the rounding may differ), so the planner sorts them into one
+// canonical order (`23 01` and `01 23` are one program) without re-listing the chain.  Codes as S2Keep::pmeta: 16 | J << 2 | I for a 4x4 gate on block bits I < J, I for a 2x2.
+constexpr int kS2ProgShift = 16, kS2ProgPermShift = 24, kS2ProgMaxSteps = 4;
+struct S2Prog {
+  int B, n;
+  int code[kS2ProgMaxSteps];
+};
+constexpr int s2_c4(int i, int j) { return 16 | (j << 2) | i; }
+// in the order of their share of the gate work in the headline plan (C4, min_chunks 64)
+constexpr S2Prog kS2Progs[] = {
+    {4, 3, {s2_c4(0, 1), s2_c4(1, 2), s2_c4(2, 3), 0}},   // the 3-gate staircase
+    {4, 2, {s2_c4(0, 1), s2_c4(2, 3), 0, 0}},             // two disjoint gates
+    {4, 2, {s2_c4(1, 2), s2_c4(2, 3), 0, 0}},             // a staircase's tail
+    {4, 3, {s2_c4(0, 3), s2_c4(0, 1), s2_c4(1, 2), 0}},   // a staircase entered from the top bit (C3's main pass)
+    {4, 2, {3, s2_c4(1, 2), 0, 0}},                       // a 2x2 beside a 4x4
+    {4, 2, {1, s2_c4(2, 3), 0, 0}},
+    {4, 2, {s2_c4(1, 2), s2_c4(0, 3), 0, 0}},             // nested disjoint gates
+    {3, 2, {s2_c4(0, 1), s2_c4(1, 2), 0, 0}},             // the 2-gate staircase of 8-element blocks
+};
+constexpr int kS2NumProgs = (int)(sizeof(kS2Progs) / sizeof(kS2Progs[0]));
+static_assert(kS2NumProgs <= 8, "program set (instruction-cache footprint)");
+// block bits a code touches
+constexpr int s2_code_bits(int code) {
+  return (code & 16) ? ((1 << (code & 3)) | (1 << ((code >> 2) & 3))) : (1 << (code & 3));
+}
+// program id and step permutation (the B word's high bits) of a plain block pass, 0 = none
+inline int s2_prog_bits(int B, const int32_t* code, int cnt) {
+  if (cnt < 1 || cnt > kS2ProgMaxSteps) return 0;
+  int c[kS2ProgMaxSteps], g[kS2ProgMaxSteps];
+  for (int q = 0; q < cnt; ++q) { c[q] = code[q]; g[q] = q; }
+  // canonical order: neighbours on disjoint bits sorted by code (a linear extension of the
+  // overlap order: overlapping gates never pass each other)
+  for (bool moved = true; moved;) {
+    moved = false;
+    for (int q = 0; q + 1 < cnt; ++q)
+      if (!(s2_code_bits(c[q]) & s2_code_bits(c[q + 1])) && c[q] > c[q + 1]) {
+        const int tc = c[q], tg = g[q];
+        c[q] = c[q + 1]; g[q] = g[q + 1];
+        c[q + 1] = tc; g[q + 1] = tg;
+        moved = true;
+      }
+  }
+  for (int id = 1; id <= kS2NumProgs; ++id) {
+    const S2Prog& p = kS2Progs[id - 1];
+    if (p.B != B || p.n != cnt) continue;
+    bool same = true;
+    for (int q = 0; q < cnt; ++q) same = same && p.code[q] == c[q];
+    if (!same) continue;
+    int perm = 0;
+    for (int q = 0; q < cnt; ++q) perm |= g[q] << (2 * q);
+    return (int)(((uint32_t)id << kS2ProgShift) | ((uint32_t)perm << kS2ProgPermShift));
+  }
+  return 0;
+}
 inline int s2_block_bits(int esz, int64_t tile_elems) {
   // 2^B elements per thread: 16 (FP32 data, tiles of >= 8192 elements) or 8
   return (esz <= 8 && tile_elems >= 8192) ? 4 : 3;

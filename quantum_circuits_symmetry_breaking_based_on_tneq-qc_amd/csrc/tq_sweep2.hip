@@ -442,7 +442,59 @@ __device__ __forceinline__ void blk_swap(T (&x)[16], int code) {
   }
 }
 
-template <typename T, int B>
+// ---- pass programs (tq_sweep2.h kS2Progs): the gate part of a plain block pass as straight-line
+// code.  The interpreter below keeps x[] in fixed registers at its gate loop's phis while a gate's
+// outputs land in rotated ones (16 v_mov_b64 per gate beside its 128 packed FMAs), reads a gate
+// code from LDS per gate and dispatches through blk_gate's switch; a program has no loop, no
+// switch and no code read, and x[] never crosses a runtime phi.
+// The unit of a program is one output column of one gate: its K coefficients (4 x 2 VGPRs for
+// complex64) are read while the previous column's FMAs run, so a program holds two columns of
+// coefficients, the block's 2^B inputs and the outputs computed so far -- 80 VGPRs at its
+// widest for complex64, where whole-gate double buffering (2 x 32 coefficient VGPRs) spilled.
+// A gate's outputs go to fresh registers (y) and replace x after its last column; in
+// straight-line code that is a renaming, not a copy.
+constexpr int s2_code_k(int code) { return (code & 16) ? 4 : 2; }
+template <typename T, int CODE, int N>
+__device__ __forceinline__ void prog_col(T (&c)[4], const T* __restrict__ cf) {
+  constexpr int K = s2_code_k(CODE);
+#pragma unroll
+  for (int k = 0; k < K; ++k) c[k] = coef(cf, k * K + N);
+}
+template <typename T, int B, int CODE, int N>
+__device__ __forceinline__ void prog_col_apply(const T (&x)[1 << B], T (&y)[1 << B], const T (&c)[4]) {
+  constexpr int K = s2_code_k(CODE), I = CODE & 3, J = K == 4 ? (CODE >> 2) & 3 : I;
+  auto slot = [](int base, int k) { return K == 4 ? base | ((k & 1) << I) | ((k >> 1) << J) : base | (k << I); };
+#pragma unroll
+  for (int r = 0; r < (1 << B) / K; ++r) {
+    const int base = deposit2<B, I, J>(r);
+    T acc = mul(x[slot(base, 0)], c[0]);
+#pragma unroll
+    for (int k = 1; k < K; ++k) mac(acc, x[slot(base, k)], c[k]);
+    y[slot(base, N)] = acc;
+  }
+}
+// columns N.. of step Q and every later step of program ID; c holds column N's coefficients
+template <typename T, int B, int ID, int Q, int N>
+__device__ __forceinline__ void prog_units(T (&x)[1 << B], T (&y)[1 << B], const T (&c)[4],
+                                           const T* __restrict__ cf0, int perm) {
+  constexpr S2Prog P = kS2Progs[ID - 1];
+  constexpr int code = P.code[Q];
+  constexpr bool last_col = N + 1 == s2_code_k(code), last = last_col && Q + 1 == P.n;
+  constexpr int Qn = last_col ? Q + 1 : Q, Nn = last_col ? 0 : N + 1;
+  T cn[4];
+  if constexpr (!last) prog_col<T, P.code[last ? Q : Qn], Nn>(cn, cf0 + ((perm >> (2 * Qn)) & 3) * kCf);
+  prog_col_apply<T, B, code, N>(x, y, c);
+  if constexpr (last_col) {
+#pragma unroll
+    for (int e = 0; e < (1 << B); ++e) x[e] = y[e];
+  }
+  if constexpr (!last) prog_units<T, B, ID, last ? Q : Qn, Nn>(x, y, cn, cf0, perm);
+}
+
+constexpr bool s2_prog_is(int id, int B) { return id >= 1 && id <= kS2NumProgs && kS2Progs[id >= 1 && id <= kS2NumProgs ? id - 1 : 0].B == B; }
+
+// ID: 0 = the interpreter (a run-time gate loop; lane blocks too), else pass program ID
+template <typename T, int B, int ID = 0>
 __device__ __forceinline__ void block_pass(T* __restrict__ buf, const T* __restrict__ cf_all, const PassHead& h,
                                            const int32_t* __restrict__ pml, const int32_t* __restrict__ lut,
                                            int logC) {
@@ -473,6 +525,14 @@ __device__ __forceinline__ void block_pass(T* __restrict__ buf, const T* __restr
     for (int e = 0; e < E; ++e) x[e] = *reinterpret_cast<const T*>(bb + (a0 ^ off(e)));
     // the element addresses are recomputed for the write-back (not held across the gates)
     asm volatile("" : "+v"(a0));
+    if constexpr (ID != 0) {
+      static_assert(kS2Progs[ID - 1].B == B, "program's block bits");
+      const int perm = pm[kS2PmB] >> kS2ProgPermShift;
+      const T* const cf0 = cf_all + first * kCf;
+      T c0[4], y[E];
+      prog_col<T, kS2Progs[ID - 1].code[0], 0>(c0, cf0 + (perm & 3) * kCf);
+      prog_units<T, B, ID, 0, 0>(x, y, c0, cf0, perm);
+    } else {
     // gates (and a lane block's swaps; the gate row advances on gates only)
     int gq = first;
     for (int q = 0; q < cnt; ++q) {
@@ -486,12 +546,13 @@ __device__ __forceinline__ void block_pass(T* __restrict__ buf, const T* __restr
       blk_gate<T, B>(x, cf_all + gq * kCf, code);
       ++gq;
     }
+    }
     // write-back in the end layout (S2Keep::pmeta [16, 22): a plain block's is its start layout)
     int be[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) be[b] = ba[b];
     int aw = a0;
-    if (lanes) {
+    if (ID == 0 && lanes) {
 #pragma unroll
       for (int b = 0; b < B; ++b) be[b] = __builtin_amdgcn_readfirstlane(pml[kS2PmAddrEnd + b]) << SH;
       const int d4 = __builtin_amdgcn_readfirstlane(pml[kS2PmLaneDelta]) << SH;
@@ -924,10 +985,26 @@ __global__ void __launch_bounds__(NT, SEQ ? 1 : 4) sweep2_kernel(S2Launch L) {
       const int bk = cur.w[kS2PmB];
       const int32_t* const lp = lut + p * kLut;   // the pass's group table (rows by pass)
       if (bk == 0) run_gate<T>(buf, cf + g * kCf, cur, lp, logC);
-      else if ((bk & 0xff) == 4) {
-        if constexpr (sizeof(T) <= 8) block_pass<T, 4>(buf, cf, cur, pmeta + p * kS2PmWords, lp, logC);
+      else {
+        // one dispatch per pass on the wave-uniform program id (0, or an id this build does not
+        // know: the interpreter)
+        const int32_t* const pml = pmeta + p * kS2PmWords;
+#define TQ_PROG(b, id)                                                                  \
+  if (s2_prog_is(id, b) && prog == id) {                                                \
+    block_pass<T, b, s2_prog_is(id, b) ? id : 0>(buf, cf, cur, pml, lp, logC);          \
+  } else
+        const int prog = (bk >> kS2ProgShift) & 0xff;
+        if ((bk & 0xff) == 4) {
+          if constexpr (sizeof(T) <= 8) {
+            TQ_PROG(4, 1) TQ_PROG(4, 2) TQ_PROG(4, 3) TQ_PROG(4, 4) TQ_PROG(4, 5) TQ_PROG(4, 6) TQ_PROG(4, 7) TQ_PROG(4, 8)
+            block_pass<T, 4>(buf, cf, cur, pml, lp, logC);
+          }
+        } else {
+          TQ_PROG(3, 1) TQ_PROG(3, 2) TQ_PROG(3, 3) TQ_PROG(3, 4) TQ_PROG(3, 5) TQ_PROG(3, 6) TQ_PROG(3, 7) TQ_PROG(3, 8)
+          block_pass<T, 3>(buf, cf, cur, pml, lp, logC);
+        }
+#undef TQ_PROG
       }
-      else block_pass<T, 3>(buf, cf, cur, pmeta + p * kS2PmWords, lp, logC);
       asm volatile("" ::: "memory");
 #ifdef TQ_S2_TIMING
       if (ch == lb && ts_rec && threadIdx.x == 0 && p < 16) {

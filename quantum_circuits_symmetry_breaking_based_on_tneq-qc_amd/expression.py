@@ -72,7 +72,8 @@ class NativePlan:
         """Plan option (tq_plan_set): "graph" (replay a captured hipGraph, default 1),
         "sweep_chain" (chain launches of small dependent sweep2 ops, default 1), "sweep_coop"
         (cooperative launches of dependent multi-chunk sweep2 levels, default 0 = TQ_S2_COOP;
-        diagnostic, measured slower)."""
+        diagnostic, measured slower), "s2_programs" (sweep2 block passes as compile-time pass
+        programs, default 1 = TQ_S2_PROG; before the first execute)."""
         check(_lib.lib().tq_plan_set(self._h, key.encode(), int(value)), "tq_plan_set")
 
     def describe(self) -> str:
