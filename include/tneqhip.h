@@ -237,6 +237,31 @@ int tq_inverse_cdf_sample(int dtype, int64_t n_rows, int64_t grid_size, const vo
                           int64_t ld_density, const void* grid_x, const float* u, void* samples,
                           int64_t samples_stride, void* stream);
 
+/* Born-rule sampling of a block of n complex amplitudes (dtype TQ_C64 / TQ_C128, contiguous,
+ * device), the consumer of tq_plan_execute's output.  With p_i = re(a_i)^2 + im(a_i)^2 in float64
+ * (complex64 widened first), C = the inclusive prefix sum of p, S1 = C_{n-1}, S2 = sum p_i^2:
+ *   index[j] = min{ i : C_i > u[j] * S1 }; when no i qualifies (u[j] >= 1, NaN, rounding) the
+ *   largest i with p_i > 0; -1 (and prob[j] = 0) when S1 is not a finite number > 0;
+ *   prob[j] = p_{index[j]};  stats (device, 2 float64) = S1, S2.
+ * u: n_draws float64 uniforms (device); index: n_draws int64 (device); prob: n_draws float64
+ * (device) or NULL.  1 <= n <= 2^31, 0 <= n_draws < 2^31 (0: only stats).  An element with
+ * p_i = 0 is never selected.  The sums use no float atomics: the same inputs give the same bits,
+ * the kernel's C is non-decreasing in i, and the bound that selects a chunk of C for a threshold
+ * is bit-identical to C at that chunk's last element (csrc/tq_born.hip).
+ * axis_qubit (HOST, n_axes distinct entries in [0, 62], n == 2^n_axes; NULL = plain indices,
+ * n_axes and base ignored): index[j] becomes the bitstring word
+ *   base | sum_a ((i >> (n_axes - 1 - a)) & 1) << axis_qubit[a]
+ * (axis 0 = the slowest axis of a row-major block; bit q of the word = qubit q; base must be 0
+ * at the axis qubits; -1 stays -1).  The table travels by value in the kernel arguments.
+ * workspace: tq_born_sample_workspace(dtype, n, n_draws) bytes of device memory, 8-byte aligned
+ * (the query is host-only: 0 and a tq_last_error message for bad arguments).  Every argument is
+ * checked before anything is launched; the launch allocates, copies and synchronises nothing, so
+ * it may be captured into a graph.                                                            */
+size_t tq_born_sample_workspace(int dtype, int64_t n, int64_t n_draws);
+int tq_born_sample(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
+                   int64_t* index, double* prob, double* stats, int n_axes, const int32_t* axis_qubit,
+                   uint64_t base, void* workspace, size_t ws_bytes, void* stream);
+
 /* Fidelity loss of the symmetry-breaking fit (symmetry_breaking_quantum.py:220-229, the loss of
  * every pruning candidate; validate_target_tensor :159-166), over n complex elements (dtype
  * TQ_C64 / TQ_C128, t = target, o = the contraction's output, both device):

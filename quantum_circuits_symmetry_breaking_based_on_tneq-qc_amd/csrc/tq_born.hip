@@ -1,0 +1,429 @@
+// Born-rule sampling of a block of amplitudes on the device: the consumer of tq_plan_execute's
+// output for SURVEY.md §8(e) ("shard bitstrings").  Replaces nothing in the reference, which has
+// no bitstring sampler; the nearest is the continuous EngineSiamese.sample
+// (tneq_qc/core/engine_siamese.py:740-915, here icdf_kernel in tq_data.hip), one draw per row on
+// a grid of <= 8192 points.  Without this entry point a user copies every 8 MB block to the host
+// and runs cumsum + searchsorted there.
+//
+//     p_i = re(a_i)^2 + im(a_i)^2 (float64; complex64 widened first, so both squares are exact)
+//     C_i = inclusive prefix sum of p,  S1 = C_{n-1},  S2 = sum p_i^2
+//     index_j = min{ i : C_i > u_j S1 }, else the last i with p_i > 0; -1 when S1 is not in (0, inf)
+//     prob_j = p_{index_j}
+//
+// Three launches, no float atomics, bitwise reproducible:
+//  * born_totals  — one workgroup (256 lanes) per chunk of 4096 elements: coalesced 16-B loads,
+//    p into LDS, chunk_scan; the chunk's total, sum p^2 and last positive element go to a slab.
+//  * born_bases   — one workgroup: the chunk ends within groups of 16 chunks (cend), the group
+//    bases (sbase), S1, S2 and the last positive element; writes stats.
+//  * born_resolve — one workgroup per chunk: every lane tests draws against the chunk's interval
+//    [Elo, Ehi); a chunk that owns a draw re-runs chunk_scan (the same device function) keeping
+//    the 4096 local values in LDS, and each owned draw binary-searches them.
+//
+// The kernel's C is defined by one nested expression, every level accumulated in index order:
+//     C_i = sbase[g] + (cbase[c] + (woff[w] + (io[l] + run_k)))
+// run_k: the lane's running sum over its 16 consecutive elements; io: the running sum of the lane
+// totals of the 64 lanes of a wave; woff: of the 4 wave totals; cbase: of the chunk totals of the
+// group (cbase[c + 1] = cend[c] = cbase[c] + total[c]); sbase: of the group totals.  At every level
+// the value at a unit's last element IS the next unit's base (the same float64 add of the same
+// operands), and a unit's first element adds a non-negative number to that base; float64 addition
+// is monotone, so C is non-decreasing in i, and the bound that selects a chunk for a threshold
+// (Ehi = sbase[g] + cend[c]) is bit-identical to C at the chunk's last element.  FP contraction is
+// off so that both passes round identically whatever the compiler does with either kernel.
+#include "tq_common.h"
+
+namespace tq {
+
+namespace {
+
+constexpr int kBornNT = 256;                     // lanes per workgroup
+constexpr int kBornPL = 16;                      // consecutive elements per lane
+constexpr int kBornChunk = kBornNT * kBornPL;    // 4096
+constexpr int kBornGroup = 16;                   // chunks per group of the base scan
+constexpr int kBornTile = 4 * kBornNT;           // draws tested per round of born_resolve
+constexpr int kBornMaxAxes = 31;
+
+struct BornAxes {
+  int8_t q[kBornMaxAxes + 1];
+};
+
+// workspace layout (all 8-byte words first, then the int32 slab)
+struct BornWs {
+  double* total;      // [nchunks]  chunk totals (chunk_scan's last local value)
+  double* s2;         // [nchunks]  chunk sums of p^2
+  double* cend;       // [nchunks]  end of chunk c within its group
+  double* sbase;      // [ngroups + 1]
+  double* meta;       // [0] = S1, [1] = last positive element (int64 bits)
+  int32_t* lastloc;   // [nchunks]  last positive element within the chunk, -1 = none
+};
+
+inline int64_t born_chunks(int64_t n) { return (n + kBornChunk - 1) / kBornChunk; }
+inline int64_t born_groups(int64_t nchunks) { return (nchunks + kBornGroup - 1) / kBornGroup; }
+
+inline size_t born_ws_bytes(int64_t n) {
+  const int64_t nc = born_chunks(n), ng = born_groups(nc);
+  const size_t words = (size_t)(3 * nc + (ng + 1) + 2);
+  return (words * 8 + (size_t)nc * 4 + 15) & ~(size_t)15;
+}
+
+inline BornWs born_ws(void* ws, int64_t n) {
+  const int64_t nc = born_chunks(n), ng = born_groups(nc);
+  BornWs w;
+  double* d = reinterpret_cast<double*>(ws);
+  w.total = d;
+  w.s2 = w.total + nc;
+  w.cend = w.s2 + nc;
+  w.sbase = w.cend + nc;
+  w.meta = w.sbase + ng + 1;
+  w.lastloc = reinterpret_cast<int32_t*>(w.meta + 2);
+  return w;
+}
+
+template <typename T>
+__device__ __forceinline__ double born_p(const T* __restrict__ amps, int64_t i) {
+#pragma clang fp contract(off)
+  using R = typename Traits<T>::R;
+  const R* __restrict__ r = reinterpret_cast<const R*>(amps) + 2 * i;
+  const double re = (double)r[0], im = (double)r[1];
+  return re * re + im * im;
+}
+
+// LDS position of chunk element e: one pad word per lane segment, so that lane l reading its
+// segment (stride 17 doubles) touches every bank once per 32 lanes
+__device__ __forceinline__ int born_pad(int e) { return e + (e >> 4); }
+
+struct BornLds {
+  double v[kBornChunk + kBornNT];   // p, then the local inclusive values
+  double lt[kBornNT];               // lane totals
+  double wt[kBornNT / 64];          // wave totals
+  double ws2[kBornNT / 64];         // wave sums of p^2
+  int wl[kBornNT / 64];             // last positive element per wave
+};
+
+// The chunk scan: loads chunk c (elements beyond n count as p = 0), leaves in L.v either nothing
+// useful (KEEP = false) or local_i = woff + (io + run_k) for every element, and returns the
+// chunk total = local value of the chunk's last element.  STATS: also the chunk's sum of p^2
+// (a fixed reduction order) and its last element with p > 0 (-1 = none), for the first pass.
+template <typename T, bool VEC, bool KEEP, bool STATS>
+__device__ __forceinline__ double chunk_scan(const T* __restrict__ amps, int64_t n, int64_t c,
+                                             BornLds& L, double& s2_out, int& last_out) {
+#pragma clang fp contract(off)
+  constexpr int EPL = 16 / (int)sizeof(T);          // elements per 16-B load
+  constexpr int NLD = kBornPL / EPL;                // loads per lane
+  const int tid = threadIdx.x;
+  const int64_t e0 = c * kBornChunk;
+  const int64_t rem = n - e0;                       // > 0
+  const T* __restrict__ a = amps + e0;
+#pragma unroll
+  for (int j = 0; j < NLD; ++j) {
+    const int e = j * (kBornNT * EPL) + tid * EPL;
+    if constexpr (VEC && EPL == 2) {
+      if (e + 2 <= rem) {
+        const float4 q = *reinterpret_cast<const float4*>(a + e);
+        const double r0 = (double)q.x, i0 = (double)q.y, r1 = (double)q.z, i1 = (double)q.w;
+        L.v[born_pad(e)] = r0 * r0 + i0 * i0;
+        L.v[born_pad(e + 1)] = r1 * r1 + i1 * i1;
+        continue;
+      }
+    }
+    if constexpr (VEC && EPL == 1) {
+      if (e < rem) {
+        const double2 q = *reinterpret_cast<const double2*>(a + e);
+        L.v[born_pad(e)] = q.x * q.x + q.y * q.y;
+        continue;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) L.v[born_pad(e + k)] = (e + k < rem) ? born_p<T>(a, e + k) : 0.0;
+  }
+  __syncthreads();
+  double* __restrict__ seg = L.v + tid * (kBornPL + 1);
+  double run = 0.0, s2 = 0.0;
+  int last = -1;
+#pragma unroll
+  for (int k = 0; k < kBornPL; ++k) {
+    const double p = seg[k];
+    run += p;
+    if constexpr (KEEP) seg[k] = run;
+    if constexpr (STATS) {
+      s2 += p * p;
+      if (p > 0.0) last = tid * kBornPL + k;
+    }
+  }
+  L.lt[tid] = run;
+  __syncthreads();
+  // io: running sum of the lane totals of this wave, in lane order (every lane walks the same
+  // 64 broadcast reads)
+  const int lane = tid & 63, w = tid >> 6;
+  double io = 0.0, acc = 0.0;
+#pragma unroll 8
+  for (int s = 0; s < 64; ++s) {
+    if (s == lane) io = acc;
+    acc += L.lt[w * 64 + s];
+  }
+  if constexpr (STATS) {
+    // sum p^2 and the last positive element of the wave: a fixed butterfly, the same every run
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+      s2 += __shfl_xor(s2, m);
+      last = max(last, __shfl_xor(last, m));
+    }
+  }
+  if (lane == 0) {
+    L.wt[w] = acc;
+    if constexpr (STATS) {
+      L.ws2[w] = s2;
+      L.wl[w] = last;
+    }
+  }
+  __syncthreads();
+  double woff = 0.0, tot = 0.0;
+#pragma unroll
+  for (int x = 0; x < kBornNT / 64; ++x) {
+    if (x == w) woff = tot;
+    tot += L.wt[x];
+  }
+  if constexpr (KEEP) {
+#pragma unroll
+    for (int k = 0; k < kBornPL; ++k) seg[k] = woff + (io + seg[k]);
+  }
+  if constexpr (STATS) {
+    s2_out = 0.0;
+    last_out = -1;
+#pragma unroll
+    for (int x = 0; x < kBornNT / 64; ++x) {
+      s2_out += L.ws2[x];
+      last_out = max(last_out, L.wl[x]);
+    }
+  }
+  return tot;
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kBornNT)
+born_totals(const T* __restrict__ amps, int64_t n, BornWs W) {
+  __shared__ BornLds L;
+  const int64_t c = blockIdx.x;
+  double s2 = 0.0;
+  int last = -1;
+  const double tot = chunk_scan<T, VEC, false, true>(amps, n, c, L, s2, last);
+  if (threadIdx.x == 0) {
+    W.total[c] = tot;
+    W.s2[c] = s2;
+    W.lastloc[c] = last;
+  }
+}
+
+__global__ void __launch_bounds__(kBornNT)
+born_bases(int64_t nchunks, int64_t ngroups, BornWs W, double* __restrict__ stats) {
+#pragma clang fp contract(off)
+  __shared__ double gt[kBornNT], gs[kBornNT];
+  __shared__ int64_t gl[kBornNT];
+  const int tid = threadIdx.x;
+  double acc0 = 0.0, s20 = 0.0;   // lane 0: running over the groups
+  int64_t last0 = -1;
+  for (int64_t g0 = 0; g0 < ngroups; g0 += kBornNT) {
+    const int64_t g = g0 + tid;
+    if (g < ngroups) {
+      // the group's slab first (independent loads), then the running sums in chunk order
+      const int64_t c0 = g * kBornGroup;
+      const int nc = (int)(nchunks - c0 < kBornGroup ? nchunks - c0 : kBornGroup);
+      double t[kBornGroup], q[kBornGroup];
+      int32_t l[kBornGroup];
+#pragma unroll
+      for (int k = 0; k < kBornGroup; ++k) {
+        const bool in = k < nc;
+        t[k] = in ? W.total[c0 + k] : 0.0;
+        q[k] = in ? W.s2[c0 + k] : 0.0;
+        l[k] = in ? W.lastloc[c0 + k] : -1;
+      }
+      double acc = 0.0, s2 = 0.0;
+      int64_t last = -1;
+#pragma unroll
+      for (int k = 0; k < kBornGroup; ++k) {
+        acc += t[k];
+        s2 += q[k];
+        if (k < nc) W.cend[c0 + k] = acc;
+        if (l[k] >= 0) last = (c0 + k) * kBornChunk + l[k];
+      }
+      gt[tid] = acc;
+      gs[tid] = s2;
+      gl[tid] = last;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      if (g0 == 0) W.sbase[0] = 0.0;
+      const int ng = (int)(ngroups - g0 < kBornNT ? ngroups - g0 : kBornNT);
+      for (int k = 0; k < ng; ++k) {
+        acc0 += gt[k];
+        W.sbase[g0 + k + 1] = acc0;
+        s20 += gs[k];
+        if (gl[k] >= 0) last0 = gl[k];
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    W.meta[0] = acc0;
+    reinterpret_cast<int64_t*>(W.meta)[1] = last0;
+    stats[0] = acc0;
+    stats[1] = s20;
+  }
+}
+
+__device__ __forceinline__ int64_t born_word(int64_t idx, int n_axes, const BornAxes& ax, uint64_t base) {
+  if (n_axes < 0) return idx;
+  uint64_t wd = base;
+  for (int a = 0; a < n_axes; ++a)
+    wd |= (uint64_t)((idx >> (n_axes - 1 - a)) & 1) << ax.q[a];
+  return (int64_t)wd;
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kBornNT)
+born_resolve(const T* __restrict__ amps, int64_t n, int64_t n_draws, const double* __restrict__ u,
+             int64_t* __restrict__ index, double* __restrict__ prob, BornWs W, int n_axes,
+             BornAxes ax, uint64_t base) {
+#pragma clang fp contract(off)
+  __shared__ BornLds L;
+  __shared__ int list[kBornTile];
+  __shared__ int cnt;
+  const int tid = threadIdx.x;
+  const int64_t c = blockIdx.x;
+  const double S1 = W.meta[0];
+  if (!(S1 > 0.0 && S1 < __builtin_huge_val())) {
+    if (c == 0)
+      for (int64_t j = tid; j < n_draws; j += kBornNT) {
+        index[j] = -1;
+        if (prob) prob[j] = 0.0;
+      }
+    return;
+  }
+  const int64_t g = c / kBornGroup;
+  const double G = W.sbase[g];
+  const double cb = (c % kBornGroup) ? W.cend[c - 1] : 0.0;
+  const double Elo = G + cb, Ehi = G + W.cend[c];
+  if (c != 0 && !(Ehi > Elo)) return;   // no mass here: no threshold selects this chunk
+  const int64_t lastpos = reinterpret_cast<const int64_t*>(W.meta)[1];
+  if (tid == 0) cnt = 0;
+  __syncthreads();
+  bool scanned = false;
+  for (int64_t j0 = 0; j0 < n_draws; j0 += kBornTile) {
+#pragma unroll
+    for (int q = 0; q < kBornTile / kBornNT; ++q) {
+      const int64_t j = j0 + q * kBornNT + tid;
+      if (j < n_draws) {
+        const double t = u[j] * S1;
+        if (Ehi > t && (c == 0 || !(Elo > t))) {
+          list[atomicAdd(&cnt, 1)] = (int)(j - j0);
+        } else if (c == 0 && !(S1 > t)) {
+          // no C_i exceeds t (u >= 1, NaN, rounding): the last element with p > 0
+          index[j] = lastpos >= 0 ? born_word(lastpos, n_axes, ax, base) : -1;
+          if (prob) prob[j] = lastpos >= 0 ? born_p<T>(amps, lastpos) : 0.0;
+        }
+      }
+    }
+    __syncthreads();
+    const int m = cnt;
+    if (m > 0) {
+      if (!scanned) {
+        double s2;
+        int last;
+        chunk_scan<T, VEC, true, false>(amps, n, c, L, s2, last);
+        __syncthreads();
+        scanned = true;
+      }
+      for (int s = tid; s < m; s += kBornNT) {
+        const int64_t j = j0 + list[s];
+        const double t = u[j] * S1;
+        // first i with C_i > t; C at the chunk's last element is Ehi > t
+        int lo = 0, hi = kBornChunk - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (G + (cb + L.v[born_pad(mid)]) > t) hi = mid; else lo = mid + 1;
+        }
+        // (the padded tail of the last chunk repeats the last element's value, so idx < n)
+        const int64_t at = c * kBornChunk + lo;
+        const int64_t idx = at < n ? at : n - 1;
+        index[j] = born_word(idx, n_axes, ax, base);
+        if (prob) prob[j] = born_p<T>(amps, idx);
+      }
+    }
+    __syncthreads();
+    if (tid == 0) cnt = 0;
+    __syncthreads();
+  }
+}
+
+template <typename T, bool VEC>
+int born_t(int64_t n, const void* amps, int64_t n_draws, const double* u, int64_t* index,
+           double* prob, double* stats, int n_axes, const BornAxes& ax, uint64_t base, void* ws,
+           hipStream_t st) {
+  const int64_t nc = born_chunks(n), ng = born_groups(nc);
+  const BornWs W = born_ws(ws, n);
+  const T* a = reinterpret_cast<const T*>(amps);
+  hipLaunchKernelGGL((born_totals<T, VEC>), dim3((unsigned)nc), dim3(kBornNT), 0, st, a, n, W);
+  TQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(born_bases, dim3(1), dim3(kBornNT), 0, st, nc, ng, W, stats);
+  TQ_HIP(hipGetLastError());
+  if (n_draws > 0) {
+    hipLaunchKernelGGL((born_resolve<T, VEC>), dim3((unsigned)nc), dim3(kBornNT), 0, st, a, n,
+                       n_draws, u, index, prob, W, n_axes, ax, base);
+    TQ_HIP(hipGetLastError());
+  }
+  return TQ_OK;
+}
+
+}  // namespace
+
+size_t born_workspace(int dtype, int64_t n, int64_t n_draws) {
+  if (dtype != TQ_C64 && dtype != TQ_C128) {
+    set_error("born_sample: amplitudes must be TQ_C64 or TQ_C128");
+    return 0;
+  }
+  if (n < 1 || n > ((int64_t)1 << 31)) {
+    set_error("born_sample: n must be in [1, 2^31]");
+    return 0;
+  }
+  if (n_draws < 0 || n_draws >= ((int64_t)1 << 31)) {
+    set_error("born_sample: n_draws must be in [0, 2^31)");
+    return 0;
+  }
+  return born_ws_bytes(n);
+}
+
+int born_launch(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
+                int64_t* index, double* prob, double* stats, int n_axes, const int32_t* axis_qubit,
+                uint64_t base, void* workspace, size_t ws_bytes, hipStream_t stream) {
+  const size_t need = born_workspace(dtype, n, n_draws);
+  if (need == 0) return TQ_ERR_INVALID;
+  TQ_CHECK_ARG(amps && stats && workspace, "born_sample: null pointer");
+  TQ_CHECK_ARG(n_draws == 0 || (u && index), "born_sample: null u / index");
+  TQ_CHECK_ARG(ws_bytes >= need, "born_sample: workspace smaller than tq_born_sample_workspace");
+  TQ_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "born_sample: workspace must be 8-byte aligned");
+  const size_t ralign = dtype == TQ_C64 ? 4 : 8;
+  TQ_CHECK_ARG(((uintptr_t)amps & (ralign - 1)) == 0, "born_sample: misaligned amplitudes");
+  BornAxes ax{};
+  int na = -1;
+  if (axis_qubit) {
+    TQ_CHECK_ARG(n_axes >= 0 && n_axes <= kBornMaxAxes && n == ((int64_t)1 << n_axes),
+                 "born_sample: n must equal 2^n_axes");
+    uint64_t seen = 0;
+    for (int a = 0; a < n_axes; ++a) {
+      const int q = axis_qubit[a];
+      TQ_CHECK_ARG(q >= 0 && q <= 62, "born_sample: axis qubit outside [0, 62]");
+      TQ_CHECK_ARG(!((seen >> q) & 1), "born_sample: repeated axis qubit");
+      seen |= (uint64_t)1 << q;
+      ax.q[a] = (int8_t)q;
+    }
+    TQ_CHECK_ARG((base & seen) == 0, "born_sample: base overlaps an axis qubit");
+    na = n_axes;
+  }
+  const bool vec = ((uintptr_t)amps & 15) == 0;
+  if (dtype == TQ_C64)
+    return vec ? born_t<c64, true>(n, amps, n_draws, u, index, prob, stats, na, ax, base, workspace, stream)
+               : born_t<c64, false>(n, amps, n_draws, u, index, prob, stats, na, ax, base, workspace, stream);
+  return vec ? born_t<c128, true>(n, amps, n_draws, u, index, prob, stats, na, ax, base, workspace, stream)
+             : born_t<c128, false>(n, amps, n_draws, u, index, prob, stats, na, ax, base, workspace, stream);
+}
+
+}  // namespace tq

@@ -487,6 +487,19 @@ int tq_inverse_cdf_sample(int dtype, int64_t n_rows, int64_t grid_size, const vo
   TQ_GUARD_END
 }
 
+size_t tq_born_sample_workspace(int dtype, int64_t n, int64_t n_draws) {
+  return tq::born_workspace(dtype, n, n_draws);
+}
+
+int tq_born_sample(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
+                   int64_t* index, double* prob, double* stats, int n_axes, const int32_t* axis_qubit,
+                   uint64_t base, void* workspace, size_t ws_bytes, void* stream) {
+  TQ_GUARD_BEGIN
+  return tq::born_launch(dtype, n, amps, n_draws, u, index, prob, stats, n_axes, axis_qubit, base,
+                         workspace, ws_bytes, (hipStream_t)stream);
+  TQ_GUARD_END
+}
+
 int tq_fidelity_forward(int dtype, int64_t n, const void* t, const void* o, double* stats, void* loss,
                         void* stream) {
   TQ_GUARD_BEGIN

@@ -213,6 +213,11 @@ int hermite_launch(int dtype, int64_t n, int K, const double* x, const double* w
 int icdf_launch(int dtype, int64_t rows, int64_t grid_size, const void* density, int64_t ld,
                 const void* grid_x, const float* u, void* out, int64_t out_stride,
                 hipStream_t stream);
+// Born-rule sampling of an amplitude block (tq_born.hip)
+size_t born_workspace(int dtype, int64_t n, int64_t n_draws);
+int born_launch(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
+                int64_t* index, double* prob, double* stats, int n_axes, const int32_t* axis_qubit,
+                uint64_t base, void* workspace, size_t ws_bytes, hipStream_t stream);
 // fidelity loss of the symmetry-breaking fit (tq_loss.hip)
 int fidelity_forward_launch(int dtype, int64_t n, const void* t, const void* o, double* stats, void* loss,
                             hipStream_t stream);

@@ -5,7 +5,8 @@ These are the device primitives the backend and the contraction plans are built 
 ``gemm`` (the GEMM under every tensordot), ``contract_pair`` (one pairwise einsum,
 BackendPyTorch.einsum with two operands, backend_pytorch.py:623-625), and the measurement-data
 kernels of EngineSiamese: ``hermite_features`` (generate_data, engine_siamese.py:133-254) and
-``inverse_cdf_sample`` (the CDF block of sample, engine_siamese.py:854-905).
+``inverse_cdf_sample`` (the CDF block of sample, engine_siamese.py:854-905).  ``born_sample`` has
+no counterpart in the reference: bitstring indices drawn from an amplitude block by the Born rule.
 """
 from __future__ import annotations
 
@@ -194,6 +195,87 @@ def inverse_cdf_sample(density: torch.Tensor, grid: torch.Tensor, u: torch.Tenso
                                           ctypes.c_void_p(_stream_ptr(dev)))
     check(rc, "tq_inverse_cdf_sample")
     return out
+
+
+def born_workspace_size(dtype: torch.dtype, n: int, n_draws: int) -> int:
+    """Bytes of device workspace one ``born_sample`` call of these sizes needs (host only)."""
+    wsb = _lib.lib().tq_born_sample_workspace(dtype_code(dtype), int(n), int(n_draws))
+    if wsb == 0:
+        raise ValueError(f"born_sample: {_lib.last_error()}")
+    return int(wsb)
+
+
+def born_sample(amps: torch.Tensor, u: torch.Tensor, *, prob=True,
+                axis_qubit: Optional[Sequence[int]] = None, base: int = 0,
+                out: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None):
+    """Draw ``len(u)`` indices of the amplitude block ``amps`` (complex64 / complex128, contiguous,
+    any shape, on the HIP device) with probability |a_i|^2 / S1, one per float64 uniform in ``u``:
+    ``index_j = min{i : C_i > u_j S1}`` with C the float64 inclusive prefix sum of
+    ``p_i = re^2 + im^2`` (include/tneqhip.h, tq_born_sample).  Runs on the current stream of
+    ``amps``' device; no host copy, no synchronisation.
+
+    ``axis_qubit`` (one qubit per axis of a 2 x 2 x ... block, axis 0 slowest) and ``base`` turn
+    every index into a bitstring word (bit q = qubit q).  ``prob``: True (allocate), False (no
+    probabilities) or a float64 buffer.  ``out`` (int64) and a ``prob`` buffer are 1-D with at
+    least len(u) elements (the first len(u) are written and returned); ``stats`` (float64, (2,))
+    and ``workspace`` (at least ``born_workspace_size`` bytes) likewise are allocated when not
+    given.  Returns ``(index_or_words, prob or None, stats)``; stats = (S1, sum p^2)."""
+    if not isinstance(amps, torch.Tensor) or not isinstance(u, torch.Tensor):
+        raise ValueError("born_sample: amps and u must be tensors")
+    dev = _require_device(amps)
+    if u.device != dev:
+        raise ValueError("born_sample: u must live on the amplitudes' device")
+    if amps.dtype not in (torch.complex64, torch.complex128):
+        raise ValueError(f"born_sample: amplitudes must be complex64 / complex128, got {amps.dtype}")
+    if u.dtype != torch.float64:
+        raise ValueError(f"born_sample: uniforms must be float64, got {u.dtype}")
+    if not amps.is_contiguous():
+        raise ValueError("born_sample: amplitudes must be contiguous")
+    if u.ndim != 1 or not u.is_contiguous():
+        raise ValueError("born_sample: u must be a contiguous 1-D tensor")
+    n, nd = amps.numel(), u.numel()
+    code = dtype_code(amps.dtype)
+    wsb = born_workspace_size(amps.dtype, n, nd)
+
+    def _buf(t, size, dtype, what, exact=False):
+        if t is None:
+            return torch.empty(size, dtype=dtype, device=dev)
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or t.ndim != 1
+                or not t.is_contiguous() or t.numel() < size or (exact and t.numel() != size)):
+            raise ValueError(f"born_sample: {what} must be a contiguous 1-D {dtype} tensor of "
+                             f"{'' if exact else 'at least '}{size} elements on {dev}")
+        return t[:size]
+
+    out = _buf(out, nd, torch.int64, "out")
+    stats = _buf(stats, 2, torch.float64, "stats", exact=True)
+    if prob is False or prob is None:
+        pr = None
+    else:
+        pr = _buf(None if prob is True else prob, nd, torch.float64, "prob")
+    if workspace is None:
+        workspace = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    elif workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("born_sample: workspace must be a contiguous tensor on the amplitudes' device")
+    base = int(base)
+    if not 0 <= base < (1 << 64):
+        raise ValueError("born_sample: base must fit 64 bits")
+    if axis_qubit is not None:
+        axes = [int(q) for q in axis_qubit]
+        if any(not -(1 << 31) <= q < (1 << 31) for q in axes):
+            raise ValueError("born_sample: axis qubit out of range")
+        n_axes, table = len(axes), i32(axes)
+    else:
+        n_axes, table = 0, None
+    rc = _lib.lib().tq_born_sample(code, n, ctypes.c_void_p(amps.data_ptr()), nd,
+                                   ctypes.c_void_p(u.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                   ctypes.c_void_p(pr.data_ptr() if pr is not None else None),
+                                   ctypes.c_void_p(stats.data_ptr()), n_axes, table, base,
+                                   ctypes.c_void_p(workspace.data_ptr()),
+                                   workspace.numel() * workspace.element_size(),
+                                   ctypes.c_void_p(_stream_ptr(dev)))
+    check(rc, "tq_born_sample")
+    return out, pr, stats
 
 
 class _FidelityLoss(torch.autograd.Function):

@@ -24,20 +24,28 @@ launches (ordinary stream-ordered copies) and the bound plans read the new value
 no re-validation of the 606 operands per block, and no `.data` rebinding trick.  Outputs are
 written on the slot's stream: `wait()` (current stream waits) or `synchronize()` before reading.
 
+`BlockSampler` is the consumer: a `BlockPipeline` whose every block is followed, on the slot's
+stream, by one Born-rule sampling call (`ops.born_sample`, csrc/tq_born.hip), so `step()` hands
+back bitstring words, their probabilities and the block's mass instead of 8 MB of amplitudes --
+nothing is copied to the host.
+
 The product path is the native plan only (no CPU fallback): the plans raise when the HIP library
 is missing.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import _lib, ops
+from ._lib import check
 from .circuits import AmplitudeTask, with_batch
 from .expression import HipContractExpression, run_group
 
-__all__ = ["BlockPipeline"]
+__all__ = ["BlockPipeline", "BlockSampler"]
 
 
 class _Slot:
@@ -102,6 +110,7 @@ class BlockPipeline:
                 outs.append(torch.empty(self.expr.out_shape, dtype=dtype, device=self.device))
             self.slots.append(_Slot(stream, pbuf, bound, outs))
         self.k = 0
+        self._closed = False
         torch.cuda.synchronize(self.device)   # the table and operands exist before any slot stream reads them
 
     def plan(self, slot: int = 0, member: int = 0):
@@ -131,6 +140,8 @@ class BlockPipeline:
         """Enqueue block blocks[k mod len(blocks)] as member k mod group of slot
         (k div group) mod inflight; launches the slot's group once it is full.  Returns that
         member's output tensor (overwritten when the slot runs again)."""
+        if self._closed:
+            raise RuntimeError("the pipeline is closed")
         k = self.k
         slot = self.slots[(k // self.group) % self.inflight]
         m = k % self.group
@@ -181,3 +192,166 @@ class BlockPipeline:
     def synchronize(self) -> None:
         self.flush()
         torch.cuda.synchronize(self.device)
+
+    def close(self) -> None:
+        """Wait for the launched groups and release every member's private plan now
+        (`NativePlan.release_now`: inside a stream capture the handle is parked and released after
+        it), not whenever the garbage collector gets to them.  `step()` then raises."""
+        if self._closed:
+            return
+        self._closed = True
+        for slot in self.slots:
+            slot.pending = []
+        if not torch.cuda.is_current_stream_capturing():
+            torch.cuda.synchronize(self.device)
+        for slot in self.slots:
+            for b in slot.bound:
+                b.plan.release_now()
+
+
+def _word_of(bits) -> int:
+    w = 0
+    for q, v in bits.items():
+        if v:
+            w |= 1 << int(q)
+    return w
+
+
+class BlockSampler(BlockPipeline):
+    """A `BlockPipeline` that samples every block it contracts: `draws` bitstrings per block with
+    probability |amplitude|^2 / (block mass), on the device.
+
+    When a slot's group is launched, one Born-rule sampling call (`tq_born_sample`, the call
+    under `ops.born_sample`) per member is enqueued on the slot's stream right behind the
+    contraction; it writes into buffers the sampler owns per (slot,
+    member).  `step()` enqueues the next block and returns that member's `(words, prob, stats)`
+    device tensors -- `draws` int64 bitstring words (bit q = qubit q: the open qubits from the
+    drawn index, the closed ones from the block's fixed bits), `draws` float64 probabilities
+    |amplitude|^2 of the drawn strings (the XEB statistic) and `stats = (S1, S2)` = (the block's
+    probability mass, sum of |amplitude|^4).  Like `BlockPipeline.step()`'s outputs they are
+    written when the group has run (`wait()` / `synchronize()`) and overwritten when the slot runs
+    again.  A block whose mass is not a finite number > 0 yields words of -1 and probabilities 0.
+
+    Uniforms: row k of `uniforms` (a `(len(blocks), draws)` float64 device tensor) serves block k;
+    without it they are drawn at launch time from a `torch.Generator` of the device seeded with
+    `seed` (the same seed and the same call sequence give the same words).
+
+    Every block gets the same number of draws: choosing WHICH block to sample, in proportion to
+    the blocks' masses, is the caller's business -- `stats[0]` is the mass they need for it.
+    Circuits of more than 63 qubits do not fit the int64 words and are refused."""
+
+    def __init__(self, task: AmplitudeTask, blocks: Sequence[int], draws: int, inflight: int = 2,
+                 group: int = 1, device: Optional[torch.device] = None, dtype: torch.dtype = torch.complex64,
+                 seed: int = 0, uniforms: Optional[torch.Tensor] = None, min_chunks: Optional[int] = None):
+        qubits = [int(q) for q in task.open_qubits] + [int(q) for q in task.fixed_bits]
+        if len(qubits) > 63 or (qubits and max(qubits) > 62):
+            raise ValueError(f"BlockSampler: {len(qubits)} qubits do not fit a 63-bit bitstring word")
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError("draws must be >= 1")
+        if dtype not in (torch.complex64, torch.complex128):
+            raise ValueError(f"BlockSampler: complex64 / complex128 amplitudes, got {dtype}")
+        super().__init__(task, blocks, inflight=inflight, group=group, device=device, dtype=dtype,
+                         min_chunks=min_chunks)
+        self.draws = draws
+        self.axis_qubit = [int(q) for q in task.open_qubits]
+        # the closed qubits' bits of every block, as a word: once, not per step
+        self.base = [_word_of(with_batch(task, b).fixed_bits) for b in self.blocks]
+        if uniforms is not None:
+            if (uniforms.dtype != torch.float64 or uniforms.device != self.device
+                    or tuple(uniforms.shape) != (len(self.blocks), draws) or not uniforms.is_contiguous()):
+                raise ValueError(f"uniforms must be a contiguous ({len(self.blocks)}, {draws}) float64 tensor on {self.device}")
+            self.gen = None
+        else:
+            self.gen = torch.Generator(self.device)
+            self.gen.manual_seed(int(seed))
+        self.uniforms = uniforms
+        n = 2 ** len(self.axis_qubit)
+        wsb = ops.born_workspace_size(dtype, n, draws)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        # generated uniforms: one refill of `_refill` launches' worth per slot, on the slot's stream
+        self._refill = 16
+        self.sbuf = []    # [slot][member] -> (words, prob, stats, workspace)
+        self.ubuf = []    # [slot] -> (_refill, group, draws) uniforms, or None
+        self._ucur = []   # [slot] -> launches served from the slot's current refill
+        self._call = []   # [slot][member] -> the constant arguments of tq_born_sample
+        vp = ctypes.c_void_p
+        self._axes = _lib.i32(self.axis_qubit)
+        self._fn = _lib.lib().tq_born_sample
+        for slot in self.slots:
+            bufs = [(torch.empty(draws, dtype=torch.int64, device=self.device), torch.empty(draws, **f64),
+                     torch.empty(2, **f64), torch.empty(wsb, dtype=torch.uint8, device=self.device))
+                    for _ in range(self.group)]
+            self.sbuf.append(bufs)
+            self.ubuf.append(torch.empty((self._refill, self.group, draws), **f64) if self.gen is not None else None)
+            self._ucur.append(self._refill)
+            self._call.append([((ops.dtype_code(dtype), n, vp(slot.outs[m].data_ptr()), draws),
+                                (vp(b[0].data_ptr()), vp(b[1].data_ptr()), vp(b[2].data_ptr()),
+                                 len(self.axis_qubit), self._axes),
+                                (vp(b[3].data_ptr()), wsb, vp(slot.stream.cuda_stream)))
+                               for m, b in enumerate(bufs)])
+        # one validated call per member (arguments, buffers, the kernels' code objects): the launches
+        # behind the contractions then pass the same arguments straight to the C ABI
+        for s, slot in enumerate(self.slots):
+            with torch.cuda.stream(slot.stream):
+                for m, b in enumerate(self.sbuf[s]):
+                    slot.outs[m].zero_()
+                    ops.born_sample(slot.outs[m], torch.zeros(draws, **f64), prob=b[1], axis_qubit=self.axis_qubit,
+                                    base=self.base[0], out=b[0], stats=b[2], workspace=b[3])
+        torch.cuda.synchronize(self.device)
+
+    def _launch(self, slot: _Slot) -> None:
+        rows = list(slot.pending)
+        if not rows:
+            return
+        super()._launch(slot)
+        s = self.slots.index(slot)
+        if self.gen is not None:
+            if self._ucur[s] == self._refill:
+                with torch.cuda.stream(slot.stream):
+                    self.ubuf[s].uniform_(0.0, 1.0, generator=self.gen)
+                self._ucur[s] = 0
+            u0 = self.ubuf[s].data_ptr() + self._ucur[s] * self.group * self.draws * 8
+            self._ucur[s] += 1
+        else:
+            u0 = self.uniforms.data_ptr()
+        for m, r in enumerate(rows):
+            head, outs, tail = self._call[s][m]
+            up = u0 + (m if self.gen is not None else r) * self.draws * 8
+            check(self._fn(*head, ctypes.c_void_p(up), *outs, self.base[r], *tail), "tq_born_sample")
+        slot.event.record(slot.stream)
+
+    def step(self):
+        """Enqueue the next block (as `BlockPipeline.step()`); returns the `(words, prob, stats)`
+        device tensors of its (slot, member)."""
+        if self._closed:
+            raise RuntimeError("the sampler is closed")
+        k = self.k
+        s, m = (k // self.group) % self.inflight, k % self.group
+        super().step()
+        return self.sbuf[s][m][:3]
+
+    def run(self, n: Optional[int] = None):
+        """Sample the next `n` blocks (default: every block once); returns host copies
+        `[(words, prob, stats), ...]` in block order, copied before a slot is reused."""
+        n = len(self.blocks) if n is None else n
+        res, pend = [], []
+
+        def drain():
+            self.synchronize()
+            res.extend(tuple(t.cpu() for t in o) for o in pend)
+            pend.clear()
+
+        for _ in range(n):
+            pend.append(self.step())
+            if self.k % self.group == 0:
+                drain()
+        if pend:
+            drain()
+        return res
+
+    def close(self) -> None:
+        """Release the pipeline's private plans and the sampler's buffers now."""
+        super().close()
+        self.sbuf, self.ubuf, self._call = [], [], []
+        self.uniforms = None
