@@ -13,8 +13,9 @@
 
 // development aid: TQ_TRACE_FILE=<path> appends a line per plan execute / destroy step (finds
 // which call a native abort comes from when the test runner swallows stderr)
+static const char* trace_path() { return getenv("TQ_TRACE_FILE"); }
 static void trace(const char* what, const void* p, int64_t v = 0) {
-  static const char* path = getenv("TQ_TRACE_FILE");
+  static const char* path = trace_path();
   if (!path) return;
   if (FILE* f = fopen(path, "a")) {
     fprintf(f, "%s %p %lld\n", what, p, (long long)v);
@@ -23,7 +24,7 @@ static void trace(const char* what, const void* p, int64_t v = 0) {
 }
 // ... and records the exception behind a std::terminate (an exception leaving a destructor)
 static const bool g_trace_terminate = [] {
-  if (!getenv("TQ_TRACE_FILE")) return false;
+  if (!trace_path()) return false;
   static std::terminate_handler prev = std::set_terminate([] {
     const char* what = "(no exception)";
     std::string msg;
@@ -37,7 +38,7 @@ static const bool g_trace_terminate = [] {
         what = "(non-std exception)";
       }
     }
-    if (FILE* f = fopen(getenv("TQ_TRACE_FILE"), "a")) {
+    if (FILE* f = fopen(trace_path(), "a")) {
       fprintf(f, "terminate: %s\n", what);
       fclose(f);
     }
@@ -62,8 +63,6 @@ bool gemm_f16();
 int gemm_f16_var();
 bool gemm_presplit_enabled();
 bool gemm_configure(const char* key, int64_t v);
-bool graphs_enabled();
-bool sweeps_enabled_global();
 }
 
 extern "C" int64_t tq_library_query(const char* key) {
@@ -75,7 +74,7 @@ extern "C" int64_t tq_library_query(const char* key) {
   if (k == "gemm_f16_var") return tq::gemm_f16_var();
   if (k == "gemm_presplit") return tq::gemm_presplit_enabled() ? 1 : 0;
   if (k == "graphs") return tq::graphs_enabled() ? 1 : 0;
-  if (k == "sweep") return tq::sweeps_enabled_global() ? 1 : 0;
+  if (k == "sweep") return tq::sweeps_enabled() ? 1 : 0;
 
   return -1;
 }

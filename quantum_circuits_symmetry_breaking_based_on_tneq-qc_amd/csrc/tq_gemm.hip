@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "tq_common.h"
+#include "tq_env.h"
 #include "tq_kclock.h"
 
 namespace tq {
@@ -28,17 +29,9 @@ namespace tq {
 // The fast path computes complex products with Gauss's 3 real multiplications (default; the C4
 // amplitudes stay within 4.0e-6 of complex128, vs 2.7e-6 for the 4-multiplication product);
 // TQ_GEMM_3M=0 selects the 4-multiplication kernel.
-static int env_flag(const char* name) {
-  const char* e = getenv(name);
-  return (e && e[0] == '0') ? 0 : 1;
-}
-static std::atomic<int> g_gemm_3m{env_flag("TQ_GEMM_3M")};
-static std::atomic<int> g_gemm_bf16{env_flag("TQ_GEMM_BF16")};
-static std::atomic<int> g_gemm_f16{env_flag("TQ_GEMM_F16")};
-static int env_int(const char* name, int dflt = 0) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+static std::atomic<int> g_gemm_3m{env_on("TQ_GEMM_3M")};
+static std::atomic<int> g_gemm_bf16{env_on("TQ_GEMM_BF16")};
+static std::atomic<int> g_gemm_f16{env_on("TQ_GEMM_F16")};
 // f16-split tile variant: 0 = 8 waves of 64 x 32 with the 4-multiplication complex product,
 // 1 = 4 waves of 64 x 64, 3 = tile 0 on a 4-slot LDS ring (one barrier per two K-steps), 2 = 4
 // waves of 64 x 64 with Gauss's 3-multiplication product, 4 = tile 0 on v_mfma_f32_16x16x32_f16
@@ -67,12 +60,8 @@ bool gemm_f16() { return g_gemm_f16.load(std::memory_order_relaxed) != 0; }
 // pre-split operands (GemmPresplit) are opt-in: measured on C4 (r02) the GEMM
 // took 1.375 ms vs 1.34-1.39 ms on the split path while the producers' f16 stores added 0.37 ms
 // of sweep time per step -- the split arithmetic is not what bounds the kernel
-static int env_on(const char* name) {
-  const char* e = getenv(name);
-  return (e && e[0] == '1') ? 1 : 0;
-}
-static std::atomic<int> g_gemm_presplit{env_on("TQ_GEMM_PRESPLIT")};
-static std::atomic<int> g_presplit_bias{env_int("TQ_PRESPLIT_BIAS")};
+static std::atomic<int> g_gemm_presplit{env_opt_in("TQ_GEMM_PRESPLIT")};
+static std::atomic<int> g_presplit_bias{env_int("TQ_PRESPLIT_BIAS", 0)};
 bool gemm_presplit_enabled() { return g_gemm_presplit.load(std::memory_order_relaxed) != 0; }
 int presplit_bias() { return g_presplit_bias.load(std::memory_order_relaxed); }
 bool gemm_configure(const char* key, int64_t v) {
@@ -147,20 +136,14 @@ inline size_t amax_bytes(int64_t batch) { return ((size_t)batch * 8 + 255) / 256
 
 // TQ_GEMM_FAST=0 disables the K-outer complex64 fast path (A/B timing of the two kernels)
 bool fast_disabled() {
-  static const int v = [] {
-    const char* e = getenv("TQ_GEMM_FAST");
-    return (e && e[0] == '0') ? 1 : 0;
-  }();
-  return v != 0;
+  static const bool v = !env_on("TQ_GEMM_FAST");
+  return v;
 }
 
 // TQ_GEMM_SKINNY=0 sends the M * N <= 16 contractions to the tiled kernels (A/B timing)
 bool skinny_disabled() {
-  static const int v = [] {
-    const char* e = getenv("TQ_GEMM_SKINNY");
-    return (e && e[0] == '0') ? 1 : 0;
-  }();
-  return v != 0;
+  static const bool v = !env_on("TQ_GEMM_SKINNY");
+  return v;
 }
 
 template <typename R>

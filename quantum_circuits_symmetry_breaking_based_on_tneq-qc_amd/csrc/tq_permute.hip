@@ -23,6 +23,7 @@
 #include <numeric>
 
 #include "tq_common.h"
+#include "tq_env.h"
 #include "tq_permute.h"
 
 namespace tq {
@@ -414,7 +415,7 @@ int build_perm_plan(int dtype, int rank, const int64_t* shape, const int64_t* ss
   }
   // 7) vector configuration: VEC source-adjacent elements per load, VEC destination-adjacent per
   //    store (16-B lane accesses), verified element by element against the scalar maps
-  for (int vec = std::min(4, 16 / esz); vec >= 2 && !getenv("TQ_PERM_NOVEC"); vec /= 2) {
+  for (int vec = std::min(4, 16 / esz); vec >= 2 && !env_set("TQ_PERM_NOVEC"); vec /= 2) {
     if (T % vec) continue;
     bool ok_v = true;
     for (int d = 0; d < n_outer && ok_v; ++d)
@@ -447,10 +448,7 @@ int build_perm_plan(int dtype, int rank, const int64_t* shape, const int64_t* ss
   P.idx64 = maxoff >= (int64_t(1) << 31);
   P.n_tiles = numel / T;
   P.tile_mul = 1;
-  if ((P.n_tiles & (P.n_tiles - 1)) == 0 && P.n_tiles > 1) {
-    const char* e = getenv("TQ_PERM_TILEMUL");
-    P.tile_mul = e ? (atoll(e) | 1) : 1;
-  }
+  if ((P.n_tiles & (P.n_tiles - 1)) == 0 && P.n_tiles > 1) P.tile_mul = env_int64("TQ_PERM_TILEMUL", 1) | 1;
   P.use_generic = false;
   return TQ_OK;
 }

@@ -1,23 +1,30 @@
-// Contraction-plan compiler and executor: the GPU-resident replacement of the reference's
+// Contraction-plan compiler: the GPU-resident replacement of the reference's
 // opt_einsum ContractExpression (tneq_qc/contractor/einsum_strategy.py:622-643, executed by
 // ComputeBackend.execute_expression, tneq_qc/backends/backend_pytorch.py:99-105).
 //
 // Compile time (host, once per expression + dtype + strides):
 //   * walks the SSA pairwise path, tracks which modes are still needed (mode reference counts),
 //     classifies every mode of each pair (batch / contracted / free / single-side sum),
+//   * marks the steps that read no sliced input (hoisted: run once per execute call, results
+//     pinned) and the two independent subtrees of the join step (branches, own arena regions),
 //   * picks per step the cheapest lowering:
 //       APPLY  one operand small (<= 32 x 32) and its contracted modes forming at most two runs
 //              in the big operand -> one streaming pass, no transpose (tq_apply.hip); the small
 //              operand is read in any layout through a gather table (no extra launch);
+//              consecutive APPLY steps on one tensor form a sweep chain, flushed as ONE op: the
+//              in-place sweep2 (s2_layout, tq_sweep2.hip), its dense form (tq_sweepd.hip) or the
+//              table sweep (tq_sweep.hip);
 //       GEMM   TTGT: reuse any operand whose layout is already [batch][M][K] / [batch][K][M]
 //              (no transpose), otherwise permute it (tq_permute.hip); operand roles and the
-//              K order are chosen to minimise transposed bytes; MFMA GEMM (tq_gemm.hip);
-//   * lays intermediates out in one arena with a first-fit allocator over their live ranges,
-//   * tabulates every permute's tile tables once (uploaded with the plan).
-// Run time: a flat list of kernel launches on one stream per slice; sliced modes are removed
-// from the input views, each slice only shifts input base pointers; slices are summed into the
-// output by the final op's beta.
-#include "tq_plan.h"
+//              K order are chosen to minimise transposed bytes; MFMA GEMM (tq_gemm.hip); a
+//              tiny-output GEMM reads both operands in place (skinny);
+//   * lays intermediates out in per-branch arenas (first fit over live ranges), adds the slice
+//     lanes' copies and lane-batched GEMMs, assigns the operand-max words (assign_amax),
+//   * orders the ops into launches by dependency level, with chain launches over runs of small
+//     hoisted sweep2 levels (build_schedule), and tabulates every table once.
+// Run time: tq_plan_exec.cpp (the launch sequence of an execute call) and tq_plan_run.cpp
+// (materialize / release, the hipGraph replay of that sequence, plan_run, plan_run_group).
+#include "tq_plan_internal.h"
 #include "tq_sweep.h"
 
 #include <algorithm>
@@ -31,6 +38,12 @@
 #include <sstream>
 
 namespace tq {
+
+// TQ_SWEEP (default 1): fused sweep chains; the one reader, also behind tq_library_query "sweep"
+bool sweeps_enabled() {
+  static const bool v = env_on("TQ_SWEEP");
+  return v;
+}
 
 namespace {
 
@@ -816,53 +829,6 @@ class Compiler {
       i = std::max(e, i + 1);
     }
   }
-  // cooperative chain launches (TQ_S2_COOP=1, default 0; tq_plan_set "sweep_coop") for levels of
-  // ops of at most TQ_S2_COOPCH chunks (default 16).  Measured r04 (C2, complex64, 26 levels in
-  // one launch of 4 workgroups): 0.379 ms against 0.363 one launch per level -- the launch gaps
-  // it removes (~1.7 us each, 46 us in all) come back as longer ops (write-through stores
-  // drained before the arrival, the poll, L2-missing loads: +1.1 us per op), so it is off
-  static bool s2_coop_enabled() {
-    static const bool v = [] {
-      const char* e = getenv("TQ_S2_COOP");
-      return e && e[0] == '1';
-    }();
-    return v;
-  }
-  static int s2_coop_max_chunks() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_COOPCH");
-      return e ? std::min(16, atoi(e)) : 16;
-    }();
-    return v;
-  }
-  // chain launches take small ops of at most this many chunks, in their one-chunk layout
-  // (TQ_S2_SEQCH, default 2).  Measured r04: C2's 29 levels of 4-chunk ops as one chain are
-  // 0.404 ms against 0.363 one launch per level on a fast box -- ~6 us of gate passes per op on
-  // ONE CU cost more than the ~3 us launch gap they save -- though 0.596 against 0.677 on a box
-  // with slow memory round trips; C3's 2-chunk levels: 0.677 against 0.684 ms
-  static int s2_seq_max_chunks() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_SEQCH");
-      return e ? atoi(e) : 2;
-    }();
-    return v;
-  }
-  // chain launches: the next op's descriptor prefetched (TQ_S2_SEQPF, default 1)
-  static bool s2_seq_prefetch() {
-    static const bool v = [] {
-      const char* e = getenv("TQ_S2_SEQPF");
-      return !(e && e[0] == '0');
-    }();
-    return v;
-  }
-  // chain launches on (TQ_S2_SEQ, default 1; tq_plan_set "sweep_chain" per plan)
-  static bool s2_seq_enabled() {
-    static const bool v = [] {
-      const char* e = getenv("TQ_S2_SEQ");
-      return !(e && e[0] == '0');
-    }();
-    return v;
-  }
 
  private:
   int note_extent(int m, int64_t e) {
@@ -1195,14 +1161,6 @@ class Compiler {
     int64_t tin_n = 1, tout_n = 1, wmax = 1;
   };
 
-  static bool sweeps_enabled() {
-    static const int v = [] {
-      const char* e = getenv("TQ_SWEEP");
-      return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return v != 0;
-  }
-
   Chain::Gate make_gate(int s, const ApplyDesc& d, const Live& Sm, const Live& Bg, bool dep) {
     Chain::Gate g;
     g.Sm = Sm;
@@ -1264,136 +1222,6 @@ class Compiler {
     int l = 0;
     while ((int64_t(1) << l) < v) ++l;
     return l;
-  }
-  static int64_t s2_small_elems() {
-    static const int64_t v = [] {
-      const char* e = getenv("TQ_S2_SMALL");
-      return e ? (int64_t)atoll(e) : (int64_t(1) << 22);
-    }();
-    return v;
-  }
-  // chunks a big sweep2 op is split into at least (TQ_S2_MINCHUNKS): 128 since r05 (the deferred
-  // C4 path's 2^19-element levels, two halves per launch: 0.766 -> 0.747 ms per block, two blocks
-  // in flight 0.565 -> 0.520; C2 / C3 +-0; 64 / 512: 0.80 / 0.88, profiles/knobs_r05.txt)
-  static int s2_min_chunks() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_MINCHUNKS");
-      return e ? atoi(e) : 128;
-    }();
-    return v;
-  }
-  // slices per batch when the per-slice working set is small (TQ_SLICE_LANES, default 32; 1 = off;
-  // C3 with the capped sweep2 launches: 1.27 ms per step at 8 lanes, 1.18 at 16; r04 with 32-op
-  // sweep2 launches: 0.778 -> 0.726 ms at 32 (two launches per per-slice level, half the GEMM /
-  // reduce / permute batches), profiles/knobs_r04.jsonl)
-  // arena the lane copies may add in total (TQ_LANE_ARENA_MB, default 6 GiB of the 288 GB):
-  // C3's 6-MiB per-slice part gets 16 lanes, C4's 1.1 GiB gets 4 (measured: 16.4 -> 15.9 ms/step)
-  static size_t lane_arena_budget() {
-    static const size_t v = [] {
-      const char* e = getenv("TQ_LANE_ARENA_MB");
-      return (size_t)(e ? std::max(0, atoi(e)) : 6144) << 20;
-    }();
-    return v;
-  }
-  static int slice_lanes() {
-    static const int v = [] {
-      const char* e = getenv("TQ_SLICE_LANES");
-      return e ? std::max(1, std::min(64, atoi(e))) : 32;
-    }();
-    return v;
-  }
-  // narrowest chunk (log2 columns) of the small-tensor rule (TQ_S2_MINLC; 1 since r04: with the
-  // 32-lane batches and 4096-element register-block tiles C2 0.399 -> 0.365 ms, C3 0.786 ->
-  // 0.700, C4 N = 8 rank 2.21 -> 2.12, profiles/knobs_r04.jsonl; r03 measured 2 better alone)
-  // TQ_S2_SWZ=0: sweep2 tiles keep the r04 column-only swizzle instead of the modeled one
-  static bool s2_swz_model() {
-    static const bool v = [] {
-      const char* e = getenv("TQ_S2_SWZ");
-      return !(e && atoi(e) == 0);
-    }();
-    return v;
-  }
-  // TQ_S2_LANEBLK=1: register blocks of 6 positions over 4 lanes (lane blocks; off by default:
-  // 28 % fewer passes on C4's big sweep ops, the same time -- DESIGN.md §3.3)
-  static bool s2_lane_blocks() {
-    static const bool v = [] {
-      const char* e = getenv("TQ_S2_LANEBLK");
-      return e && atoi(e) != 0;
-    }();
-    return v;
-  }
-  // TQ_S2_WAVELOCAL=0: a workgroup barrier between every two sweep2 passes
-  static bool s2_wave_local() {
-    static const bool v = [] {
-      const char* e = getenv("TQ_S2_WAVELOCAL");
-      return !(e && atoi(e) == 0);
-    }();
-    return v;
-  }
-  static int s2_min_logc() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_MINLC");
-      return e ? std::max(0, std::min(5, atoi(e))) : 1;
-    }();
-    return v;
-  }
-  // ... for tiles of >= 2^9 positions (TQ_S2_MINLC_BIG, default 0: one column): such a chunk
-  // holds >= 512 elements per column, so a narrower chunk halves a workgroup's gate-pass VALU
-  // (passes are VALU-issue bound, probes/pass_probe.hip) and doubles the workgroups.  Measured
-  // r04 (C2: 26 levels of 1024-position tiles, 2 -> 1 column, 4 -> 8 chunks): 0.323 -> 0.303 ms;
-  // applied to every small tensor it left C3 / the C4 N = 8 rank +-0.4 % (not kept there)
-  static int s2_min_logc_big() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_MINLC_BIG");
-      return e ? std::max(0, std::min(5, atoi(e))) : 0;
-    }();
-    return v;
-  }
-  // narrowest chunk (log2 columns) of a sweep2 op before the tile / min-chunk caps (TQ_S2_LC):
-  // 7 since r03 (C3's per-slice ops, 128-element tiles: 32 -> 128 columns per chunk, 1.16 ->
-  // 1.04 ms per step with the capped launches; C4 and C2 +-0; 8-10 no better)
-  static int s2_base_logc() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_LC");
-      return e ? std::max(0, std::min(10, atoi(e))) : 7;
-    }();
-    return v;
-  }
-  static bool s2_blocks_enabled() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_BLOCKS");
-      return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return v != 0;
-  }
-  static bool s2_epi_enabled() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_EPI");
-      return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return v != 0;
-  }
-  static bool s2_enabled() {
-    static const int v = [] {
-      const char* e = getenv("TQ_SWEEP2");
-      return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return v != 0;
-  }
-  // the pre-split boundary GEMM (TQ_GEMM_PLANES=0: the GEMM-side split kernel instead)
-  static bool planes_enabled() {
-    static const int v = [] {
-      const char* e = getenv("TQ_GEMM_PLANES");
-      return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return v != 0;
-  }
-  static bool s2_dense_enabled() {
-    static const int v = [] {
-      const char* e = getenv("TQ_S2_DENSE");
-      return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return v != 0;
   }
   // Dense form of a sweep chain (tq_sweepd.hip): complex64, a small input tile (tin <= 16), an
   // output tile of <= 256, a big tensor (>= 2^20 output elements), and the six lowest column bits
@@ -1460,15 +1288,6 @@ class Compiler {
       ++r;
     }
     return r;
-  }
-
-  // TQ_S2_REORDER (default 1): commute a chain's square gates into fuller register blocks
-  static bool s2_reorder_on() {
-    static const bool v = [] {
-      const char* e = getenv("TQ_S2_REORDER");
-      return !(e && e[0] == '0');
-    }();
-    return v;
   }
 
   // Register blocks take CONSECUTIVE square gates whose positions fit B bits (s2_layout
@@ -1718,10 +1537,7 @@ class Compiler {
     // TQ_S2_B4MIN: the smallest tile (elements) that gets 16-element register blocks (default
     // 4096 since r04: a 4096-element tile then leaves half the threads idle in its block passes,
     // but needs fewer passes -- C2 0.386 -> 0.370 ms, C4 N = 8 rank -0.3 %; 8192 before)
-    static const int64_t b4min = [] {
-      const char* e = getenv("TQ_S2_B4MIN");
-      return e ? (int64_t)atoll(e) : (int64_t)4096;
-    }();
+    static const int64_t b4min = env_int64("TQ_S2_B4MIN", 4096);
     const int64_t tile_elems = int64_t(1) << (lc + used);
     const int B = (P_.esz <= 8 && tile_elems >= b4min) ? 4 : s2_block_bits((int)P_.esz, tile_elems);
     auto kmask_of = [&](int j) {
@@ -2190,7 +2006,7 @@ class Compiler {
         }
         group_lut(pp.order, d.k.lut[j]);
       }
-      if (getenv("TQ_S2_DUMP") && out) {
+      if (s2_dump() && out) {
         fprintf(stderr, "s2 op: %d gates, %d passes, logC %d, used %d:", d.ngates, d.npass, d.logC, used);
         for (const PPlan& pp : plan) {
           fprintf(stderr, " |%s", pp.lanes ? "L" : "");
@@ -2242,7 +2058,7 @@ class Compiler {
         d.nsync += sync;
       }
     }
-    if (getenv("TQ_DEBUG_S2")) {
+    if (env_set("TQ_DEBUG_S2")) {
       fprintf(stderr, "S2 cols=2^%d logC=%d used=%d epi=%d ld:", d.colbits, d.logC, used, d.epi);
       for (int t = 0; t < d.nld; ++t) fprintf(stderr, " %lld/%x", (long long)d.ld_w[t], d.ld_code[t]);
       fprintf(stderr, " | st:");
@@ -2603,13 +2419,6 @@ class Compiler {
   // A GEMM step whose output is tiny (M * N <= 16, no batch modes, no single-side sums) and whose
   // operands would need a permute: one strided skinny op reads both in place (bit weights from the
   // operands' own strides; every M / N / K mode a power of two).  true: emitted (*rc its status)
-  static bool skinny_strided_enabled() {
-    static const int v = [] {
-      const char* e = getenv("TQ_SKINNY_STRIDED");
-      return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return v != 0;
-  }
   bool skinny_step(int s, const Live* A, const Live* B, const std::set<int>& sA, const std::set<int>& sB,
                    const std::vector<int>& bord, const std::vector<int>& mord, const std::vector<int>& nord,
                    const std::vector<int>& kord, bool final, Live& res, int* rc) {
@@ -2882,10 +2691,7 @@ int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, cons
   a.sliced.assign(sliced_modes, sliced_modes + n_sliced);
   P.group_hint = group_hint;
   P.min_chunks = min_chunks;
-  static const bool prog_default = [] {   // TQ_S2_PROG=0: every block pass on the interpreter
-    const char* e = getenv("TQ_S2_PROG");
-    return !(e && e[0] == '0');
-  }();
+  static const bool prog_default = env_on("TQ_S2_PROG");   // TQ_S2_PROG=0: every block pass on the interpreter
   plan_s2_programs(P, prog_default);
   return TQ_OK;
 }
@@ -2930,7 +2736,7 @@ int64_t plan_s2_prog_passes(const Plan& P, int id) {
 int64_t plan_s2_gate_work(const Plan& P, bool programs_only) {
   double w = 0;
   std::map<std::string, double> hist;
-  const bool dump = getenv("TQ_S2_DUMP") != nullptr && !programs_only;
+  const bool dump = s2_dump() && !programs_only;
   for_s2_descs(P, [&](const Op& op, const S2Desc& d, bool dflt) {
     if (!dflt) return;
     for (int p = 0; p < d.npass; ++p) {
@@ -3010,1093 +2816,6 @@ void plan_planes_layout(Plan& P) {
   // every lane-batch size up to the lane count: a partial batch may pick more K splits (r05c)
   P.planes_sc_off = P.planes_ws_off + al(planes_gemm_workspace(g.M, g.N, g.K, (int64_t)lanes));
   P.planes_bytes = P.planes_sc_off + al(lanes * 2 * sizeof(int32_t));
-}
-
-uint64_t next_plan_serial();
-
-int plan_materialize(Plan& P, void* arena, void* tables, hipStream_t stream) {
-  TQ_HIP(hipGetDevice(&P.device));
-  P.serial = next_plan_serial();
-  if (arena || tables) {
-    P.d_arena = arena;
-    P.d_tables = tables;
-    P.owns_device = false;
-  } else {
-    P.owns_device = true;
-    if (P.arena_bytes) TQ_HIP(hipMalloc(&P.d_arena, P.arena_bytes));
-    if (P.table_bytes) TQ_HIP(hipMalloc(&P.d_tables, P.table_bytes));
-  }
-  if (P.table_bytes) {
-    std::vector<char> host(P.table_bytes, 0);
-    for (size_t i = 0; i < P.perms.size(); ++i)
-      if (perm_plan_table_bytes(P.perms[i])) perm_plan_pack_table(P.perms[i], host.data() + P.perm_tab_off[i]);
-    for (size_t i = 0; i < P.gtabs.size(); ++i)
-      std::memcpy(host.data() + P.gtab_off[i], P.gtabs[i].data(), P.gtabs[i].size() * sizeof(int32_t));
-    for (size_t i = 0; i < P.stabs.size(); ++i)
-      std::memcpy(host.data() + P.stab_off[i], P.stabs[i].data(), P.stabs[i].size());
-    TQ_HIP(hipMemcpyAsync(P.d_tables, host.data(), P.table_bytes, hipMemcpyHostToDevice, stream));
-    TQ_HIP(hipStreamSynchronize(stream));
-  }
-  if (P.n_ps && !P.h_bad) TQ_HIP(hipHostMalloc((void**)&P.h_bad, P.n_slices * sizeof(uint32_t), hipHostMallocDefault));
-  // the pre-split boundary GEMM's planes, partials and scale words (plan-owned plans only)
-  if (P.planes_gemm >= 0 && P.owns_device && !P.d_planes) {
-    plan_planes_layout(P);
-    if (hipMalloc(&P.d_planes, P.planes_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      P.d_planes = nullptr;   // no room: the GEMM-side split path runs instead
-    }
-  }
-  return TQ_OK;
-}
-
-int plan_profile_read(Plan& P, int kind, double* ms, int64_t* launches, double* flops,
-                      double* bytes) {
-  double t = 0, f = 0, b = 0;
-  int64_t n = 0;
-  for (auto& ev : P.ev_used) {
-    if (kind >= 0 && ev.kind != kind) continue;
-    TQ_HIP(hipEventSynchronize(ev.b));
-    float e = 0;
-    TQ_HIP(hipEventElapsedTime(&e, ev.a, ev.b));
-    t += e; f += ev.flops; b += ev.bytes; ++n;
-  }
-  if (ms) *ms = t;
-  if (launches) *launches = n;
-  if (flops) *flops = f;
-  if (bytes) *bytes = b;
-  return TQ_OK;
-}
-
-bool sweeps_enabled_global() {
-  const char* e = getenv("TQ_SWEEP");
-  return !(e && e[0] == '0');
-}
-
-namespace {
-
-bool graphs_disabled() {
-  static const int v = [] {
-    const char* e = getenv("TQ_GRAPH");
-    return (e && e[0] == '0') ? 1 : 0;
-  }();
-  return v != 0;
-}
-
-}  // namespace
-bool graphs_enabled() { return !graphs_disabled(); }
-namespace {
-
-// HIP release calls: the first failure is recorded (tq_last_error) and reported; a resource is
-// forgotten only once its release succeeded, so a release refused mid-way (e.g. by a stream
-// capture elsewhere in the process: HIP refuses hipGraphExecDestroy / hipFree while any stream
-// captures in global mode) can be retried later with nothing leaked or freed twice
-int rel(hipError_t e, const char* what, int& rc) {
-  if (e == hipSuccess) return 1;
-  if (rc == TQ_OK) set_error(std::string("HIP error ") + hipGetErrorString(e) + " releasing " + what);
-  rc = TQ_ERR_HIP;
-  return 0;
-}
-
-int drop_graph_entry(Plan::GraphEntry& g) {
-  int rc = TQ_OK;
-  if (g.done && rel(hipEventSynchronize(g.done), "graph event", rc) && rel(hipEventDestroy(g.done), "graph event", rc))
-    g.done = nullptr;
-  if (g.exec && rel(hipGraphExecDestroy(g.exec), "graph exec", rc)) g.exec = nullptr;
-  if (g.graph && rel(hipGraphDestroy(g.graph), "graph", rc)) g.graph = nullptr;
-  if (rc == TQ_OK) g = Plan::GraphEntry{};
-  return rc;
-}
-
-int drop_graph(Plan& P) {
-  int rc = TQ_OK;
-  std::vector<Plan::GraphEntry> keep;
-  for (auto& g : P.graphs)
-    if (drop_graph_entry(g) != TQ_OK) {
-      rc = TQ_ERR_HIP;
-      keep.push_back(g);
-    }
-  P.graphs.swap(keep);
-  return rc;
-}
-
-}  // namespace
-
-int plan_release(Plan& P) {
-  int rc = drop_graph(P);
-  if (P.cap_stream && rel(hipStreamDestroy(P.cap_stream), "capture stream", rc)) P.cap_stream = nullptr;
-  auto drop_events = [&](std::vector<Plan::Ev>& v) {
-    std::vector<Plan::Ev> keep;
-    for (auto& ev : v) {
-      if (ev.a && rel(hipEventDestroy(ev.a), "event", rc)) ev.a = nullptr;
-      if (ev.b && rel(hipEventDestroy(ev.b), "event", rc)) ev.b = nullptr;
-      if (ev.a || ev.b) keep.push_back(ev);
-    }
-    v.swap(keep);
-  };
-  drop_events(P.ev_used);
-  drop_events(P.ev_free);
-  {
-    std::vector<hipStream_t> ks;
-    for (auto s : P.side_streams)
-      if (!rel(hipStreamDestroy(s), "group side stream", rc)) ks.push_back(s);
-    P.side_streams.swap(ks);
-    std::vector<hipEvent_t> ke;
-    for (auto e : P.side_events)
-      if (!rel(hipEventDestroy(e), "group event", rc)) ke.push_back(e);
-    P.side_events.swap(ke);
-  }
-  if (P.owns_device) {
-    if (P.d_arena && rel(hipFree(P.d_arena), "arena", rc)) P.d_arena = nullptr;
-    if (P.d_tables && rel(hipFree(P.d_tables), "tables", rc)) P.d_tables = nullptr;
-  } else {
-    P.d_arena = P.d_tables = nullptr;
-  }
-  if (P.h_bad && rel(hipHostFree(P.h_bad), "host flag", rc)) P.h_bad = nullptr;
-  if (P.d_planes && rel(hipFree(P.d_planes), "planes", rc)) P.d_planes = nullptr;
-  return rc;
-}
-
-
-int plan_enqueue(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
-                 int64_t s_step, int accumulate, hipStream_t stream);
-// the pre-split boundary GEMM runs: the plan has one, its buffers exist, the plan option is on
-// and the pre-split (predicted-scale) mode of the split kernel is not running
-static bool planes_active(const Plan& P) {
-  return P.planes_gemm >= 0 && P.d_planes != nullptr && P.use_planes && !P.run_mode;
-}
-int plan_launch(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
-                int64_t s_step, int accumulate, hipStream_t stream);
-
-int plan_run(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
-             int64_t s_step, int accumulate, hipStream_t stream) {
-  TQ_CHECK_ARG(s_step >= 1, "slice_step");
-  TQ_CHECK_ARG(s_begin >= 0 && s_end <= P.n_slices, "slice range");
-  TQ_CHECK_ARG(P.arena_bytes == 0 || P.d_arena, "plan not materialized");
-  {
-    // a plan's arena, tables and graphs live on one device; running it with another device
-    // current would hand that device foreign pointers
-    int cur = -1;
-    TQ_HIP(hipGetDevice(&cur));
-    TQ_CHECK_ARG(P.device < 0 || cur == P.device,
-                 "plan was materialized on device " + std::to_string(P.device) +
-                     " but device " + std::to_string(cur) + " is current");
-  }
-  // pre-split GEMM operands (Op::ps_cand) when every candidate still takes the f16 split path
-  // under the current library switches, and the stream is not being captured by the caller
-  // (the window check below synchronizes)
-  P.run_mode = 0;
-  if (P.n_ps && P.h_bad) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    TQ_HIP(hipStreamIsCapturing(stream, &cs));
-    bool ok = cs == hipStreamCaptureStatusNone;
-    for (const Op& op : P.ops)
-      if (op.ps_cand && !gemm_c64_presplit_ok(op.transA, op.transB, op.M, op.N, op.K, op.batch, op.lda, op.ldb))
-        ok = false;
-    P.run_mode = ok ? 1 : 0;
-  }
-  TQ_TRY(plan_launch(P, inputs, out, s_begin, s_end, s_step, accumulate, stream));
-  if (P.use_coop && !P.coop_once.empty() && P.d_tables) {
-    // cooperative chain launches (opt-in) rely on their workgroups being co-resident; a wait
-    // that gave up (sync[1], counted by the kernel) means the op read stale data: the execute
-    // synchronizes to check (outside a caller's capture) and fails instead of returning it
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    TQ_HIP(hipStreamIsCapturing(stream, &cs));
-    if (cs == hipStreamCaptureStatusNone) {
-      uint32_t gaveup = 0;
-      for (size_t r = 0; r < P.coop_once.size(); ++r) {
-        uint32_t w = 0;
-        char* slot = (char*)P.d_tables + P.sync_off + r * Plan::kSyncSlot + 4;
-        TQ_HIP(hipMemcpyAsync(&w, slot, 4, hipMemcpyDeviceToHost, stream));
-        TQ_HIP(hipStreamSynchronize(stream));
-        if (w) TQ_HIP(hipMemsetAsync(slot, 0, 4, stream));
-        gaveup += w;
-      }
-      if (gaveup) {
-        TQ_HIP(hipStreamSynchronize(stream));
-        set_error("cooperative sweep chain: " + std::to_string(gaveup) +
-                  " workgroup wait(s) gave up (workgroups not co-resident); the result is invalid -- "
-                  "run with sweep_coop 0");
-        return TQ_ERR_HIP;
-      }
-    }
-  }
-  if (P.run_mode) {
-    // slices whose operand max left its scale window produced zeros: add them on the split path
-    const uint32_t* dbad = reinterpret_cast<const uint32_t*>((const char*)P.d_tables + P.bad_off);
-    TQ_HIP(hipMemcpyAsync(P.h_bad, dbad, P.n_slices * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    TQ_HIP(hipStreamSynchronize(stream));
-    // a lane-batched candidate GEMM flags its whole batch in the batch's first slice (the
-    // other lanes' words are not written): batches are consecutive groups of `lanes` slices
-    bool batched = false;
-    for (const Op& op : P.ops) batched = batched || (op.ps_cand && op.lane_batch);
-    std::vector<int64_t> redo, batch;
-    for (int64_t sl = s_begin; sl < s_end; sl += s_step * std::max(1, P.lanes)) {
-      batch.clear();
-      for (int64_t q = sl; q < s_end && (int64_t)batch.size() < std::max(1, P.lanes); q += s_step) batch.push_back(q);
-      for (int64_t q : batch)
-        if (batched ? P.h_bad[batch[0]] != 0 : P.h_bad[q] != 0) redo.push_back(q);
-    }
-    P.run_mode = 0;
-    for (int64_t sl : redo) TQ_TRY(plan_enqueue(P, inputs, out, sl, sl + 1, 1, 1, stream));
-    P.ps_fallbacks += (int64_t)redo.size();
-  }
-  return TQ_OK;
-}
-
-int plan_launch(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
-                int64_t s_step, int accumulate, hipStream_t stream) {
-  if (P.profile || !P.use_graph || graphs_disabled())
-    return plan_enqueue(P, inputs, out, s_begin, s_end, s_step, accumulate, stream);
-  // a caller's stream capture (a torch.cuda.graph around the call): the launches go straight
-  // into that capture -- a graph of the plan's own, built on its side stream and launched into
-  // the capturing stream, ran once at capture time and was not part of the caller's replays
-  {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    TQ_HIP(hipStreamIsCapturing(stream, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-      return plan_enqueue(P, inputs, out, s_begin, s_end, s_step, accumulate, stream);
-  }
-  Plan::GraphKey key;
-  key.inputs.assign(inputs, inputs + P.n_inputs);
-  key.out = out; key.b = s_begin; key.e = s_end; key.s = s_step; key.acc = accumulate;
-  key.mode = P.run_mode;
-  key.planes = planes_active(P) ? 1 : 0;
-  key.seq = P.use_seq;
-  key.coop = P.use_coop;
-  constexpr size_t kMaxGraphs = 8;
-  Plan::GraphEntry* hit = nullptr;
-  for (auto& g : P.graphs) if (g.key == key) hit = &g;
-  if (!hit) {
-    if (P.graphs.size() >= kMaxGraphs) {  // evict the least recently used (after it finished)
-      auto lru = std::min_element(P.graphs.begin(), P.graphs.end(),
-                                  [](const Plan::GraphEntry& a, const Plan::GraphEntry& b) { return a.used < b.used; });
-      drop_graph_entry(*lru);
-      P.graphs.erase(lru);
-    }
-    if (!P.cap_stream) TQ_HIP(hipStreamCreateWithFlags(&P.cap_stream, hipStreamNonBlocking));
-    TQ_HIP(hipStreamBeginCapture(P.cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = plan_enqueue(P, inputs, out, s_begin, s_end, s_step, accumulate, P.cap_stream);
-    hipGraph_t g = nullptr;
-    const hipError_t ce = hipStreamEndCapture(P.cap_stream, &g);
-    if (rc != TQ_OK) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    TQ_HIP(ce);
-    Plan::GraphEntry e;
-    e.key = key;
-    e.graph = g;
-    TQ_HIP(hipGraphInstantiate(&e.exec, g, nullptr, nullptr, 0));
-    TQ_HIP(hipEventCreateWithFlags(&e.done, hipEventDisableTiming));
-    P.graphs.push_back(e);
-    hit = &P.graphs.back();
-    ++P.graph_builds;
-  }
-  hit->used = ++P.graph_clock;
-  TQ_HIP(hipGraphLaunch(hit->exec, stream));
-  TQ_HIP(hipEventRecord(hit->done, stream));
-  ++P.graph_launches;
-  return TQ_OK;
-}
-
-// ---- executor: one plan, or a GROUP of plans compiled from the same network (blocks as lanes).
-// A group executes its plans' schedules in lockstep: every sweep2 level (and dense-sweep level,
-// and chain launch) of all instances is ONE launch whose op list holds every instance's ops --
-// the slice-lane mechanism with an instance index -- so G amplitude blocks in flight cost the
-// launches of one; the other ops (GEMM, permute, lane sum, ...) run per instance.  A group of one
-// plan is exactly the single-plan executor.
-namespace {
-
-bool sweep_lanes_on();   // TQ_SWEEP_LANES (default 1): per-slice table sweeps lane-merged
-
-struct Inst {
-  Plan* P = nullptr;
-  const void* const* inputs = nullptr;
-  void* out = nullptr;
-  std::vector<std::vector<int64_t>> lane_in_off;
-  std::vector<int64_t> lane_sl;
-  int cur = 0;             // lane the launches address
-  double beta_out = 0.0;   // the first slice of a non-accumulating call overwrites the output
-  bool first = true;
-  bool lanes_summed = false;
-};
-
-class Exec {
- public:
-  Exec(std::vector<Inst>& insts, hipStream_t stream) : I_(insts), st_(stream), P0_(*insts[0].P) {}
-
-  int run(int64_t s_begin, int64_t s_end, int64_t s_step, int accumulate);
-
- private:
-  std::vector<Inst>& I_;
-  hipStream_t st_;
-  Plan& P0_;
-  int lane_gemm_ = 1;   // > 1: the GEMM launch below covers that many lanes
-
-  size_t esz() const { return P0_.esz; }
-  char* ptr(const Inst& x, const BufRef& b) const {
-    const Plan& P = *x.P;
-    switch (b.kind) {
-      case BUF_INPUT: return (char*)x.inputs[b.index] + (x.lane_in_off[x.cur][b.index] + b.off) * P.esz;
-      case BUF_ARENA: return (char*)P.d_arena + P.lane_phys + (size_t)x.cur * P.lane_stride + b.off * P.esz;
-      case BUF_PINNED: return (char*)P.d_arena + b.off * P.esz;
-      case BUF_OUTPUT: return (char*)x.out + b.off * P.esz;
-      case BUF_TABLE: return (char*)P.d_tables + b.off;
-    }
-    return nullptr;
-  }
-  static void set_lane(Inst& x, int j) {
-    x.cur = j;
-    x.beta_out = (x.first && x.cur == 0) ? 0.0 : 1.0;
-  }
-  void set_lane_all(int j) {
-    for (auto& x : I_) set_lane(x, j);
-  }
-  static uint32_t* amax_word(const Inst& x, int w) {
-    return reinterpret_cast<uint32_t*>((char*)x.P->d_tables + x.P->amax_off) + w;
-  }
-  // lane j's copy of max word w: per-slice words have one set per lane (the pre-split mode keeps
-  // one shared set: its scales are predicted per batch)
-  static int lane_amax_stride(const Inst& x, int w) {
-    return (w >= x.P->n_amax_once && !x.P->run_mode) ? x.P->n_amax_slice : 0;
-  }
-  static uint32_t* amax_lane(const Inst& x, int w, int j) { return amax_word(x, w + j * lane_amax_stride(x, w)); }
-  // scale word of per-slice max word w; window flag of slice q
-  static int32_t* sc_word(const Inst& x, int w) {
-    return reinterpret_cast<int32_t*>((char*)x.P->d_tables + x.P->sc_off) + (w - x.P->n_amax_once);
-  }
-  static uint32_t* bad_word(const Inst& x, int64_t q) {
-    return reinterpret_cast<uint32_t*>((char*)x.P->d_tables + x.P->bad_off) + q;
-  }
-  // the pre-split boundary GEMM: lane j's planes of operand r (0 = A, 1 = B) and scale words
-  static _Float16* planes_ptr(const Inst& x, int j, int r) {
-    const Plan& P = *x.P;
-    return reinterpret_cast<_Float16*>((char*)P.d_planes + (size_t)j * P.planes_lane_bytes +
-                                       (r ? (size_t)12 * P.planes_n[0] : 0));
-  }
-  static int32_t* planes_sc(const Inst& x, int j, int r) {
-    return reinterpret_cast<int32_t*>((char*)x.P->d_planes + x.P->planes_sc_off) + 2 * j + r;
-  }
-
-  // profiling (HIP events on the stream; the group's first plan holds the records)
-  Plan::Ev ev_begin(int kind) {
-    Plan::Ev ev{};
-    if (P0_.ev_free.empty()) {
-      if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) ev.kind = -1;
-    } else {
-      ev = P0_.ev_free.back();
-      P0_.ev_free.pop_back();
-    }
-    if (ev.kind == -1) return ev;
-    ev.kind = kind;
-    ev.flops = 0;
-    ev.bytes = 0;
-    return ev;
-  }
-
-  int launch_one(Inst& x, const Op& op);
-  int fill_s2(const Inst& x, S2Op& o, const Op& op, int stab) const;
-  SweepArgs sweep_args(const Inst& x, const Op& op, double beta) const;
-  int sweep_lanes_ = 0;   // > 0: the OP_SWEEP entry below runs every lane of the batch in one launch
-  // per-instance work of a group: member k > 0 on side stream k - 1 (forked from and joined back
-  // into the execution stream: parallel branches of the captured graph), member 0 on the stream
-  hipStream_t ost_ = nullptr;   // the stream launch_one / lane sums use (st_ unless forked)
-  template <typename F>
-  int each_instance(F&& f);
-  int launch_chain(int b, int e, int coop);
-  int launch(const std::vector<int>& grp);
-};
-
-// the table-driven sweep op's launch record for instance x's current lane
-SweepArgs Exec::sweep_args(const Inst& x, const Op& op, double beta) const {
-  const Plan& P = *x.P;
-      SweepArgs a;
-      const char* blob = (const char*)P.d_tables + P.stab_off[op.stab];
-      a.X = ptr(x, op.a);
-      a.Y = ptr(x, op.c);
-      a.ncols = op.ncols;
-      auto lg = [](int64_t v) {
-        if (v <= 0 || (v & (v - 1))) return -1;
-        int l = 0;
-        while ((int64_t(1) << l) < v) ++l;
-        return l;
-      };
-      a.nruns = op.nruns;
-      for (int r = 0; r < op.nruns; ++r) {
-        a.run_ext[r] = op.run_ext[r]; a.run_in[r] = op.run_in[r]; a.run_out[r] = op.run_out[r];
-        a.run_shift[r] = lg(op.run_ext[r]);
-      }
-      a.tin = op.tin;
-      a.tout = op.tout;
-      a.tin_shift = lg(op.tin);
-      a.tout_shift = lg(op.tout);
-      a.tabs = (const int32_t*)(blob + op.tabs_at);
-      a.tab_len = op.tab_len;
-      a.tin_off = (const int64_t*)blob;
-      a.tout_off = (const int64_t*)(blob + op.tout_off_at);
-      a.ngates = (int)op.sgates.size();
-      for (int j = 0; j < a.ngates; ++j) {
-        const SweepGate& g = op.sgates[j];
-        a.G[j] = ptr(x, g.g);
-        a.gidx[j] = g.gtab >= 0 ? (const int32_t*)((char*)P.d_tables + P.gtab_off[g.gtab]) : nullptr;
-        a.K[j] = g.K; a.N[j] = g.N; a.W[j] = g.W;
-        a.tab_at[j] = (int)g.tab_off;
-      }
-      // power-of-two outer extents: per-bit column-offset weights
-      {
-        bool p2 = true;
-        int nb = 0;
-        for (int r = 0; r < op.nruns && p2; ++r) {
-          const int l = lg(op.run_ext[r]);
-          if (l < 0 || nb + l > 48) { p2 = false; break; }
-          for (int b = 0; b < l; ++b) {
-            a.w_in[nb + b] = op.run_in[r] << b;
-            a.w_out[nb + b] = op.run_out[r] << b;
-          }
-          nb += l;
-        }
-        a.colbits = p2 ? nb : -1;
-      }
-      a.load_colfast = op.load_colfast;
-      a.store_colfast = op.store_colfast;
-      a.use_beta = beta != 0.0;
-      a.beta = beta;
-  return a;
-}
-
-template <typename F>
-int Exec::each_instance(F&& f) {
-  static const bool fork = [] {
-    const char* e = getenv("TQ_GROUP_FORK");
-    return !(e && e[0] == '0');
-  }();
-  const int n = (int)I_.size();
-  if (n == 1 || !fork) {
-    ost_ = st_;
-    for (auto& x : I_) TQ_TRY(f(x));
-    return TQ_OK;
-  }
-  Plan& P = P0_;
-  while ((int)P.side_streams.size() < n - 1) {
-    hipStream_t s = nullptr;
-    TQ_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    P.side_streams.push_back(s);
-  }
-  while ((int)P.side_events.size() < n) {
-    hipEvent_t e = nullptr;
-    TQ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    P.side_events.push_back(e);
-  }
-  TQ_HIP(hipEventRecord(P.side_events[0], st_));
-  int rc = TQ_OK;
-  for (int k = 1; k < n && rc == TQ_OK; ++k) {
-    hipStream_t s = P.side_streams[k - 1];
-    TQ_HIP(hipStreamWaitEvent(s, P.side_events[0], 0));
-    ost_ = s;
-    rc = f(I_[k]);
-    TQ_HIP(hipEventRecord(P.side_events[k], s));
-  }
-  ost_ = st_;
-  if (rc == TQ_OK) rc = f(I_[0]);
-  for (int k = 1; k < n; ++k) TQ_HIP(hipStreamWaitEvent(st_, P.side_events[k], 0));
-  return rc;
-}
-
-int Exec::launch_one(Inst& x, const Op& op) {
-  Plan& P = *x.P;
-  const hipStream_t st = ost_ ? ost_ : st_;
-  const double beta = op.writes_output ? x.beta_out : 0.0;
-  const bool planes_on = planes_active(P);
-  if (planes_on && op.kind == OP_GEMM && &op == &P.ops[P.planes_gemm]) {
-    // lane batch: entries = the batch's lanes (planes and scale words at their lane strides),
-    // the combine sums them into lane 0's result when the plan sums the lanes (Op::lane_sum)
-    const int j0 = lane_gemm_ > 1 ? 0 : x.cur;
-    PlanesGemmArgs a;
-    a.A = planes_ptr(x, j0, 0);
-    a.B = planes_ptr(x, j0, 1);
-    a.sA = a.sB = (int64_t)(P.planes_lane_bytes / 2);
-    a.psA = P.planes_n[0];
-    a.psB = P.planes_n[1];
-    a.lda = op.lda;
-    a.ldb = op.ldb;
-    a.M = (int)op.M;
-    a.N = (int)op.N;
-    a.K = op.K;
-    a.batch = lane_gemm_;
-    a.W = reinterpret_cast<float*>((char*)P.d_planes + P.planes_ws_off);
-    a.ws_bytes = P.planes_sc_off - P.planes_ws_off;
-    PlanesCombineArgs c;
-    c.sc_a = planes_sc(x, j0, 0);
-    c.sc_b = planes_sc(x, j0, 1);
-    c.sc_stride = 2;
-    c.C = ptr(x, op.c);
-    c.ldc = op.ldc;
-    c.sC = (int64_t)(P.lane_stride / P.esz);
-    c.lane_sum = lane_gemm_ > 1 && op.lane_sum;
-    c.beta = (float)beta;
-    return planes_gemm_launch(a, c, st);
-  }
-  switch (op.kind) {
-    case OP_PERMUTE:
-      TQ_TRY(perm_plan_launch(P.perms[op.perm], (char*)P.d_tables + P.perm_tab_off[op.perm], ptr(x, op.a),
-                              ptr(x, op.c), beta, st));
-      break;
-    case OP_GEMM: {
-      if (op.skinny) {
-        SkinnyArgs a = op.sk;
-        a.A = ptr(x, op.a);
-        a.B = ptr(x, op.b);
-        a.C = ptr(x, op.c);
-        a.W = op.ws_bytes ? ptr(x, op.ws) : nullptr;
-        a.beta = beta;
-        TQ_TRY(skinny_strided_launch(P.dtype, a, st));
-        break;
-      }
-      GemmPresplit ps;
-      const bool pre = P.run_mode && op.ps_cand;
-      if (pre) {
-        ps.sc_a = sc_word(x, op.amax_a);
-        ps.sc_b = sc_word(x, op.amax_b);
-        ps.bad = bad_word(x, x.lane_sl[x.cur]);
-      }
-      if (lane_gemm_ > 1) {   // every lane of the batch in one launch (Op::lane_batch)
-        const int64_t ls = (int64_t)(P.lane_stride / P.esz);
-        // pre-split: one window flag for the batch, in its first slice's word
-        TQ_TRY(gemm_launch(P.dtype, op.transA, op.transB, op.M, op.N, op.K, lane_gemm_, ptr(x, op.a), op.lda,
-                           op.a.kind == BUF_ARENA ? ls : 0, ptr(x, op.b), op.ldb, op.b.kind == BUF_ARENA ? ls : 0,
-                           beta, ptr(x, op.c), op.ldc, ls, (char*)P.d_arena + P.lane_ws_off, P.lane_ws_bytes, st,
-                           op.amax_a >= 0 ? amax_word(x, op.amax_a) : nullptr,
-                           op.amax_b >= 0 ? amax_word(x, op.amax_b) : nullptr, pre ? &ps : nullptr,
-                           op.amax_a >= 0 ? lane_amax_stride(x, op.amax_a) : 0,
-                           op.amax_b >= 0 ? lane_amax_stride(x, op.amax_b) : 0));
-        break;
-      }
-      TQ_TRY(gemm_launch(P.dtype, op.transA, op.transB, op.M, op.N, op.K, op.batch, ptr(x, op.a), op.lda, op.sA,
-                         ptr(x, op.b), op.ldb, op.sB, beta, ptr(x, op.c), op.ldc, op.sC,
-                         op.ws_bytes ? ptr(x, op.ws) : nullptr, op.ws_bytes, st,
-                         op.amax_a >= 0 ? amax_lane(x, op.amax_a, x.cur) : nullptr,
-                         op.amax_b >= 0 ? amax_lane(x, op.amax_b, x.cur) : nullptr, pre ? &ps : nullptr));
-      break;
-    }
-    case OP_APPLY:
-      TQ_TRY(apply_launch(P.dtype, op.O, op.K, op.M, op.K2, op.I, op.N, ptr(x, op.a), ptr(x, op.b),
-                          op.gtab >= 0 ? (const int32_t*)((char*)P.d_tables + P.gtab_off[op.gtab]) : nullptr,
-                          ptr(x, op.c), beta, st));
-      break;
-    case OP_AXPY:
-      TQ_TRY(axpy_launch(P.dtype, op.n, ptr(x, op.a), ptr(x, op.c), beta, st));
-      break;
-    case OP_SWEEP: {
-      const SweepArgs a = sweep_args(x, op, beta);
-      TQ_TRY(sweep_launch(P.dtype, a, st));
-      break;
-    }
-    default:
-      set_error("internal: op kind");
-      return TQ_ERR_INVALID;
-  }
-  return TQ_OK;
-}
-
-// a sweep2 op's launch record from descriptor stabs[stab] (the instance's current lane)
-int Exec::fill_s2(const Inst& x, S2Op& o, const Op& op, int stab) const {
-  const Plan& P = *x.P;
-  o.desc = (const S2Desc*)((const char*)P.d_tables + P.stab_off[stab]);
-  o.X = ptr(x, op.a);
-  o.Y = ptr(x, op.c);
-  const S2Desc* hd = reinterpret_cast<const S2Desc*>(P.stabs[stab].data());
-  for (size_t g = 0; g < op.sgates.size(); ++g) {
-    o.G[g] = ptr(x, op.sgates[g].g);
-    int mx = 0;
-    for (int t = 0; t < hd->gate[g].K * hd->gate[g].N; ++t) mx = std::max(mx, hd->gate[g].gidx[t] + 1);
-    if (mx > kS2GateRaw) {
-      set_error("internal: sweep2 gate tensor too large");
-      return TQ_ERR_INVALID;
-    }
-    o.gnum[g] = (uint8_t)mx;
-  }
-  o.beta = op.writes_output ? x.beta_out : 0.0;
-  o.use_beta = o.beta != 0.0;
-  o.amax = op.amax_word >= 0 ? amax_lane(x, op.amax_word, x.cur) : nullptr;
-  o.split_sc = P.run_mode && op.ps_gemm >= 0 ? sc_word(x, op.amax_word) : nullptr;
-  // host-built lane / chunk-base tables behind the descriptor (TQ_S2_HOSTTAB=0: computed in the
-  // kernel, the r05 prologue)
-  static const bool host_tabs = [] {
-    const char* e = getenv("TQ_S2_HOSTTAB");
-    return !(e && e[0] == '0');
-  }();
-  const char* blob = (const char*)P.d_tables + P.stab_off[stab];
-  o.rows = host_tabs ? (hd->npass & 0xff) | (hd->ngates & 0xff) << 8 | (hd->colbits & 0xff) << 16 : 0;
-  o.lanes = host_tabs && hd->aux_lanes ? reinterpret_cast<const uint4*>(blob + hd->aux_lanes) : nullptr;
-  o.cbase = host_tabs && hd->aux_cb ? reinterpret_cast<const int64_t*>(blob + hd->aux_cb) : nullptr;
-  return TQ_OK;
-}
-
-// Plan::seq_once run [b, e): its ops in order, a workgroup per (instance, stream), one launch (as
-// many instances per launch as kS2SeqMaxStreams allows); or (coop >= 0) Plan::coop_once run
-// `coop`: its ops in order on coop_width workgroups each, one launch per instance
-int Exec::launch_chain(int b, int e, int coop) {
-  const bool prof = (P0_.profile >> (int)OP_SWEEP) & 1;
-  if (coop >= 0) {
-    for (auto& x : I_) {
-      Plan& P = *x.P;
-      Plan::Ev ev{};
-      if (prof) {
-        ev = ev_begin((int)OP_SWEEP);
-        TQ_HIP(hipEventRecord(ev.a, st_));
-      }
-      const int w = P.coop_width[coop];
-      S2Launch L;
-      L.seq = 1;
-      L.sync = reinterpret_cast<uint32_t*>((char*)P.d_tables + P.sync_off + (size_t)coop * Plan::kSyncSlot);
-      for (int i = b; i < e; ++i) {
-        const Op& op = P.ops[P.sched_once[i][0]];
-        S2Op& o = L.op[L.nops];
-        TQ_TRY(fill_s2(x, o, op, op.stab));
-        o.block_begin = 0;
-        o.nblocks = w;
-        o.lds_io = kS2Coop | (L.nops * w) << 8 | (op.lds_io & 4);   // (bit 2: set by the planner)
-        ++L.nops;
-        ev.flops += op.flops;
-        ev.bytes += op.bytes;
-      }
-      L.sync_total = L.nops * w;
-      TQ_TRY(sweep2_launch(P.dtype, L, st_));
-      if (prof) {
-        TQ_HIP(hipEventRecord(ev.b, st_));
-        P0_.ev_used.push_back(ev);
-      }
-    }
-    return TQ_OK;
-  }
-  int nstreams = 1, nops = 0;
-  for (int i = b; i < e; ++i)
-    for (int j : P0_.sched_once[i]) {
-      nstreams = std::max(nstreams, P0_.seq_stream[j] + 1);
-      ++nops;
-    }
-  const int per = std::max(1, std::min(kS2SeqMaxStreams / nstreams, kS2MaxOps / std::max(1, nops)));
-  for (size_t k0 = 0; k0 < I_.size(); k0 += (size_t)per) {
-    Plan::Ev ev{};
-    if (prof) {
-      ev = ev_begin((int)OP_SWEEP);
-      TQ_HIP(hipEventRecord(ev.a, st_));
-    }
-    S2Launch L;
-    L.seq = 1;
-    for (size_t k = k0; k < std::min(I_.size(), k0 + (size_t)per); ++k) {
-      const Inst& x = I_[k];
-      const Plan& P = *x.P;
-      for (int i = b; i < e; ++i)
-        for (int j : P.sched_once[i]) {
-          const Op& op = P.ops[j];
-          S2Op& o = L.op[L.nops++];
-          TQ_TRY(fill_s2(x, o, op, op.stab1));
-          o.lds_io = op.lds_io;
-          // an LDS hand-off moves the whole tensor: the kernel's first-chunk path only
-          if ((o.lds_io & 3) && reinterpret_cast<const S2Desc*>(P.stabs[op.stab1].data())->nchunks != 1) {
-            set_error("internal: sweep2 LDS hand-off on a multi-chunk layout");
-            return TQ_ERR_INVALID;
-          }
-          o.block_begin = (int)(k - k0) * nstreams + P.seq_stream[j];   // the (instance, stream) workgroup
-          o.nblocks = 1;
-          ev.flops += op.flops;
-          ev.bytes += op.bytes;
-        }
-    }
-    TQ_TRY(sweep2_launch(P0_.dtype, L, st_));
-    if (prof) {
-      TQ_HIP(hipEventRecord(ev.b, st_));
-      P0_.ev_used.push_back(ev);
-    }
-  }
-  return TQ_OK;
-}
-
-// one entry of the schedule: a single op (per instance), or independent sweep2 ops of every
-// instance (and, merged across the batch, of every lane) in one launch
-int Exec::launch(const std::vector<int>& grp) {
-  const Op& op0 = P0_.ops[grp[0]];
-  const int pkind = op0.kind == OP_SWEEP2 ? (int)OP_SWEEP : op0.kind;
-  const int nl = (int)I_[0].lane_sl.size();
-  Plan::Ev ev{};
-  const bool prof = (P0_.profile >> pkind) & 1;
-  bool lanes_merge = op0.kind == OP_SWEEP2 && nl > 1 && !op0.invariant;
-  for (int j : grp) lanes_merge = lanes_merge && !P0_.ops[j].writes_output;
-  if (prof) {
-    ev = ev_begin(pkind);
-    // a lane-batched GEMM or a sweep level merged across the batch's lanes does every lane's
-    // work; a group does every instance's
-    const int mult = (lanes_merge ? nl : sweep_lanes_ > 1 ? sweep_lanes_ : lane_gemm_) * (int)I_.size();
-    for (int j : grp) {
-      ev.flops += P0_.ops[j].flops * mult;
-      ev.bytes += P0_.ops[j].bytes * mult;
-    }
-    TQ_HIP(hipEventRecord(ev.a, st_));
-  }
-  if (op0.kind == OP_SWEEP2) {
-    // (instance, lane, op) triples of this level: every lane's ops when the level is merged
-    // across the batch, else each instance's current lane; at most kS2MaxOps per launch
-    struct Item { int k, lane, q; };
-    std::vector<Item> items, dense;
-    for (int k = 0; k < (int)I_.size(); ++k)
-      for (int j = 0; j < (lanes_merge ? nl : 1); ++j)
-        for (int q : grp) (P0_.ops[q].s2_dense ? dense : items).push_back({k, lanes_merge ? j : I_[k].cur, q});
-    std::vector<int> keep(I_.size());
-    for (size_t k = 0; k < I_.size(); ++k) keep[k] = I_[k].cur;
-    // dense ops (tq_sweepd.hip): their own launches, at most two input tile sizes each
-    // (TQ_S2D_MIX=0: one)
-    static const bool s2d_mix = [] {
-      const char* e = getenv("TQ_S2D_MIX");
-      return !(e && e[0] == '0');
-    }();
-    static const bool s2d_nt = [] {
-      const char* e = getenv("TQ_S2D_NT");
-      return e && e[0] == '1';
-    }();
-    while (!dense.empty()) {
-      S2DLaunch L;
-      const int tin = P0_.ops[dense[0].q].tin;
-      int tin2 = 0;
-      std::vector<Item> rest;
-      int blocks = 0;
-      for (auto& it : dense) {
-        Inst& x = I_[it.k];
-        const Plan& P = *x.P;
-        const Op& op = P.ops[it.q];
-        if (op.tin != tin && tin2 == 0 && s2d_mix && !s2d_nt) tin2 = op.tin;
-        if ((op.tin != tin && op.tin != tin2) || L.nops == kS2MaxOps) {
-          rest.push_back(it);
-          continue;
-        }
-        set_lane(x, it.lane);
-        S2DOp& o = L.op[L.nops++];
-        o.desc = (const S2Dense*)((const char*)P.d_tables + P.stab_off[op.stab]);
-        o.X = ptr(x, op.a);
-        o.M = ptr(x, op.b);
-        o.Y = ptr(x, op.c);
-        o.tin = op.tin;
-        o.tout = op.tout;
-        o.block_begin = blocks;
-        o.nblocks = s2d_blocks(op.ncols);
-        o.ncols = op.ncols;
-        blocks += o.nblocks;
-        o.beta = op.writes_output ? x.beta_out : 0.0;
-        o.use_beta = o.beta != 0.0;
-        o.amax = op.amax_word >= 0 ? amax_lane(x, op.amax_word, x.cur) : nullptr;
-        o.split_sc = P.run_mode && op.ps_gemm >= 0 ? sc_word(x, op.amax_word) : nullptr;
-        if (planes_active(P) && op.planes_role) {
-          o.planes = planes_ptr(x, x.cur, op.planes_role - 1);
-          o.pstride = P.planes_n[op.planes_role - 1];
-          o.amax_in = amax_lane(x, op.planes_in_amax, x.cur);
-          o.sc_out = planes_sc(x, x.cur, op.planes_role - 1);
-          o.amax = nullptr;
-        }
-      }
-      TQ_TRY(sweepd_launch(P0_.dtype, L, st_));
-      dense.swap(rest);
-    }
-    for (size_t i0 = 0; i0 < items.size(); i0 += kS2MaxOps) {
-      S2Launch L;
-      L.nops = (int)std::min<size_t>(kS2MaxOps, items.size() - i0);
-      int blocks = 0;
-      for (int q = 0; q < L.nops; ++q) {
-        const Item& it = items[i0 + q];
-        Inst& x = I_[it.k];
-        set_lane(x, it.lane);
-        const Op& op = x.P->ops[it.q];
-        S2Op& o = L.op[q];
-        TQ_TRY(fill_s2(x, o, op, op.stab));
-        o.block_begin = blocks;
-        o.nblocks = s2_blocks(op.s2_nchunks);
-        blocks += o.nblocks;
-      }
-      TQ_TRY(sweep2_launch(P0_.dtype, L, st_));
-    }
-    for (size_t k = 0; k < I_.size(); ++k) set_lane(I_[k], keep[k]);
-  } else if (op0.kind == OP_SWEEP && sweep_lanes_ > 1) {
-    // the per-slice table sweep of every lane in one launch (grid.y = lane; SweepLanes)
-    TQ_TRY(each_instance([&](Inst& x) -> int {
-      const Op& op = x.P->ops[grp[0]];
-      const int keep = x.cur;
-      SweepLanes ls;
-      ls.n = sweep_lanes_;
-      for (int j = 0; j < sweep_lanes_; ++j) {
-        set_lane(x, j);
-        ls.X[j] = ptr(x, op.a);
-        ls.Y[j] = ptr(x, op.c);
-        for (size_t g = 0; g < op.sgates.size(); ++g) ls.G[j][g] = ptr(x, op.sgates[g].g);
-      }
-      set_lane(x, 0);
-      const SweepArgs a = sweep_args(x, op, 0.0);
-      set_lane(x, keep);
-      return sweep_launch_lanes(x.P->dtype, a, ls, ost_ ? ost_ : st_);
-    }));
-  } else {
-    TQ_TRY(each_instance([&](Inst& x) -> int { return launch_one(x, x.P->ops[grp[0]]); }));
-  }
-  if (prof) {
-    TQ_HIP(hipEventRecord(ev.b, st_));
-    P0_.ev_used.push_back(ev);
-  }
-  return TQ_OK;
-}
-
-int Exec::run(int64_t s_begin, int64_t s_end, int64_t s_step, int accumulate) {
-  const int ns = (int)P0_.sliced.size();
-  for (auto& x : I_) x.first = !accumulate;
-  if (s_begin >= s_end) {
-    for (auto& x : I_)
-      if (!accumulate && x.P->out_numel) TQ_HIP(hipMemsetAsync(x.out, 0, x.P->out_numel * esz(), st_));
-    return TQ_OK;
-  }
-  // Slices run in batches of P.lanes (slice lanes, Plan::lanes): lane j owns its own copy of the
-  // per-slice arena part, the batch's sweep2 levels share launches across lanes, other ops run
-  // lane by lane in lane order (so output accumulation keeps its order)
-  const int64_t nlanes = std::max(1, P0_.lanes);
-  std::vector<int64_t> in_off;
-  for (int64_t s0 = s_begin; s0 < s_end; s0 += s_step * nlanes) {
-    for (auto& x : I_) {
-      const Plan& P = *x.P;
-      x.lane_sl.clear();
-      x.lane_in_off.clear();
-      in_off.assign(P.n_inputs, 0);
-      for (int64_t sl = s0; sl < s_end && (int64_t)x.lane_sl.size() < nlanes; sl += s_step) {
-        // decode slice id (row-major over sliced modes) -> per-input element offsets
-        std::vector<int64_t> idx(ns);
-        int64_t rem = sl;
-        for (int q = ns - 1; q >= 0; --q) {
-          idx[q] = rem % P.sliced_ext[q];
-          rem /= P.sliced_ext[q];
-        }
-        for (int i = 0; i < P.n_inputs; ++i) {
-          int64_t o = 0;
-          for (int q = 0; q < ns; ++q) o += idx[q] * P.inputs[i].slice_stride[q];
-          in_off[i] = o;
-        }
-        x.lane_sl.push_back(sl);
-        x.lane_in_off.push_back(in_off);
-      }
-      set_lane(x, 0);
-      x.lanes_summed = false;
-    }
-    const int nl = (int)I_[0].lane_sl.size();
-    if (s0 == s_begin) {
-      // max words are zeroed by a kernel, not hipMemsetAsync: with the zeroing as a memset node
-      // of the plan's captured graph, replays left the f16-split GEMM a max of 0 or one too small
-      // (all-zero / all-NaN outputs; mis-ordered node or carried-over max: DESIGN.md §5)
-      // one launch for the hoisted part's words and (not pre-split) the first batch's per-slice
-      // words behind them
-      for (auto& x : I_) {
-        const int n = x.P->n_amax_once + (x.P->run_mode ? 0 : x.P->n_amax_slice * nl);
-        TQ_TRY(zero_words_launch(amax_word(x, 0), n, st_));
-      }
-      size_t run = 0, crun = 0;
-      for (int i = 0; i < (int)P0_.sched_once.size();) {
-        while (P0_.use_seq && run < P0_.seq_once.size() && P0_.seq_once[run].first < i) ++run;
-        if (P0_.use_seq && run < P0_.seq_once.size() && P0_.seq_once[run].first == i) {
-          TQ_TRY(launch_chain(i, P0_.seq_once[run].second, -1));
-          i = P0_.seq_once[run].second;
-          continue;
-        }
-        while (P0_.use_coop && crun < P0_.coop_once.size() && P0_.coop_once[crun].first < i) ++crun;
-        if (P0_.use_coop && crun < P0_.coop_once.size() && P0_.coop_once[crun].first == i) {
-          TQ_TRY(launch_chain(i, P0_.coop_once[crun].second, (int)crun));
-          i = P0_.coop_once[crun].second;
-          continue;
-        }
-        TQ_TRY(launch(P0_.sched_once[i]));
-        ++i;
-      }
-    }
-    // per-slice max words: one set per lane (pre-split mode: one set shared by the batch's
-    // lanes, max-ed over all of them -- an upper bound of every lane's operand)
-    for (auto& x : I_) {
-      const Plan& P = *x.P;
-      if (P.n_amax_slice && P.run_mode)   // scales from the previous slice's max, then max = 0
-        TQ_TRY(presplit_prep_launch(amax_word(x, P.n_amax_once), sc_word(x, P.n_amax_once), P.n_amax_slice, st_));
-      else if (P.n_amax_slice && s0 != s_begin)   // (the first batch's: zeroed above)
-        TQ_TRY(zero_words_launch(amax_word(x, P.n_amax_once), P.n_amax_slice * nl, st_));
-    }
-    for (auto& grp : P0_.sched_slice) {
-      const Op& op0 = P0_.ops[grp[0]];
-      bool merged = op0.kind == OP_SWEEP2;
-      for (int j : grp) merged = merged && !P0_.ops[j].writes_output;
-      if (merged || nl == 1) {
-        set_lane_all(0);
-        TQ_TRY(launch(grp));
-        bool sums = false;
-        for (int j : grp) sums = sums || P0_.ops[j].lane_sum;
-        if (merged && nl > 1 && sums)
-          TQ_TRY(each_instance([&](Inst& x) -> int {
-            for (int j : grp)
-              if (x.P->ops[j].lane_sum) {   // a lane-merged level whose lanes an output permute sums
-                TQ_TRY(lane_sum_launch(x.P->dtype, x.P->ops[j].nc, ptr(x, x.P->ops[j].c),
-                                       (int64_t)(x.P->lane_stride / esz()), nl, ost_));
-                x.lanes_summed = true;
-              }
-            return TQ_OK;
-          }));
-      } else if (op0.kind == OP_GEMM && op0.lane_batch) {
-        set_lane_all(0);
-        lane_gemm_ = nl;
-        const int rc = each_instance([&](Inst& x) -> int {
-          TQ_TRY(launch_one(x, x.P->ops[grp[0]]));
-          if (op0.lane_sum) {
-            // (the pre-split GEMM's combine has summed the lanes already)
-            if (!(planes_active(*x.P) && grp[0] == x.P->planes_gemm))
-              TQ_TRY(lane_sum_launch(x.P->dtype, op0.nc, ptr(x, op0.c), (int64_t)(x.P->lane_stride / esz()), nl,
-                                     ost_));
-            x.lanes_summed = true;
-          }
-          return TQ_OK;
-        });
-        lane_gemm_ = 1;
-        TQ_TRY(rc);
-      } else if (op0.lane_once && I_[0].lanes_summed) {
-        set_lane_all(0);
-        TQ_TRY(launch(grp));
-      } else if (op0.kind == OP_SWEEP && grp.size() == 1 && !op0.writes_output && sweep_lanes_on() &&
-                 nl <= kSweepMaxLanes) {
-        // a per-slice table sweep whose lanes write their own copies: one launch for the batch
-        set_lane_all(0);
-        sweep_lanes_ = nl;
-        const int rc = launch(grp);
-        sweep_lanes_ = 0;
-        TQ_TRY(rc);
-      } else {
-        for (int j = 0; j < nl; ++j) {
-          set_lane_all(j);
-          TQ_TRY(launch(grp));
-        }
-      }
-    }
-    for (auto& x : I_) x.first = false;
-  }
-  return TQ_OK;
-}
-
-bool sweep_lanes_on() {
-  static const bool v = [] {
-    const char* e = getenv("TQ_SWEEP_LANES");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-// the plans of a group are the same compiled network (identical op lists and schedules)
-bool same_structure(const Plan& a, const Plan& b) {
-  if (a.dtype != b.dtype || a.ops.size() != b.ops.size() || a.sched_once != b.sched_once ||
-      a.sched_slice != b.sched_slice || a.lanes != b.lanes || a.n_slices != b.n_slices ||
-      a.seq_once != b.seq_once || a.seq_stream != b.seq_stream || a.use_seq != b.use_seq ||
-      a.use_coop != b.use_coop || a.coop_once != b.coop_once || a.n_inputs != b.n_inputs ||
-      planes_active(a) != planes_active(b) || a.planes_gemm != b.planes_gemm)
-    return false;
-  for (size_t i = 0; i < a.ops.size(); ++i)
-    if (a.ops[i].kind != b.ops[i].kind || a.ops[i].stab != b.ops[i].stab || a.ops[i].stab1 != b.ops[i].stab1 ||
-        a.ops[i].invariant != b.ops[i].invariant || a.ops[i].writes_output != b.ops[i].writes_output)
-      return false;
-  return true;
-}
-
-}  // namespace
-
-int plan_enqueue(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
-                 int64_t s_step, int accumulate, hipStream_t stream) {
-  std::vector<Inst> I(1);
-  I[0].P = &P;
-  I[0].inputs = inputs;
-  I[0].out = out;
-  Exec ex(I, stream);
-  return ex.run(s_begin, s_end, s_step, accumulate);
-}
-
-int group_enqueue(Plan* const* plans, int n, const void* const* const* inputs, void* const* outs, int64_t s_begin,
-                  int64_t s_end, int64_t s_step, int accumulate, hipStream_t stream) {
-  std::vector<Inst> I((size_t)n);
-  for (int k = 0; k < n; ++k) {
-    I[k].P = plans[k];
-    I[k].inputs = inputs[k];
-    I[k].out = outs[k];
-  }
-  Exec ex(I, stream);
-  return ex.run(s_begin, s_end, s_step, accumulate);
-}
-
-uint64_t next_plan_serial() {
-  static std::atomic<uint64_t> c{0};
-  return ++c;
-}
-
-int plan_run_group(Plan* const* plans, int n, const void* const* const* inputs, void* const* outs, int64_t s_begin,
-                   int64_t s_end, int64_t s_step, int accumulate, hipStream_t stream) {
-  TQ_CHECK_ARG(n >= 1 && plans && inputs && outs, "empty group");
-  if (n == 1) return plan_run(*plans[0], inputs[0], outs[0], s_begin, s_end, s_step, accumulate, stream);
-  Plan& P0 = *plans[0];
-  TQ_CHECK_ARG(s_step >= 1, "slice_step");
-  TQ_CHECK_ARG(s_begin >= 0 && s_end <= P0.n_slices, "slice range");
-  int cur = -1;
-  TQ_HIP(hipGetDevice(&cur));
-  for (int k = 0; k < n; ++k) {
-    Plan& P = *plans[k];
-    TQ_CHECK_ARG(P.arena_bytes == 0 || P.d_arena, "plan not materialized");
-    TQ_CHECK_ARG(P.device < 0 || cur == P.device, "a group plan was materialized on another device");
-    for (int q = 0; q < k; ++q)
-      TQ_CHECK_ARG(plans[q] != plans[k] && outs[q] != outs[k], "a group runs distinct plans into distinct outputs");
-    P.run_mode = 0;   // no pre-split (predicted-scale) GEMM mode in a group
-    TQ_CHECK_ARG(same_structure(P0, P), "the plans of a group must be compiled from the same network");
-  }
-  TQ_CHECK_ARG(!P0.use_coop, "cooperative chain launches do not run in a group");
-  const bool eager = P0.profile || !P0.use_graph || graphs_disabled();
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  TQ_HIP(hipStreamIsCapturing(stream, &cs));
-  if (eager || cs != hipStreamCaptureStatusNone)
-    return group_enqueue(plans, n, inputs, outs, s_begin, s_end, s_step, accumulate, stream);
-  // one hipGraph of the whole group, cached in the first plan under every member's serial,
-  // inputs and output (a serial is never reused, so a replay cannot address a freed plan)
-  Plan::GraphKey key;
-  for (int k = 0; k < n; ++k) {
-    key.inputs.insert(key.inputs.end(), inputs[k], inputs[k] + plans[k]->n_inputs);
-    key.group.push_back(outs[k]);
-    key.group.push_back(reinterpret_cast<const void*>((uintptr_t)plans[k]->serial));
-  }
-  key.out = outs[0]; key.b = s_begin; key.e = s_end; key.s = s_step; key.acc = accumulate;
-  key.planes = planes_active(P0) ? 1 : 0;
-  key.seq = P0.use_seq;
-  constexpr size_t kMaxGraphs = 8;
-  Plan::GraphEntry* hit = nullptr;
-  for (auto& g : P0.graphs) if (g.key == key) hit = &g;
-  if (!hit) {
-    if (P0.graphs.size() >= kMaxGraphs) {
-      auto lru = std::min_element(P0.graphs.begin(), P0.graphs.end(),
-                                  [](const Plan::GraphEntry& a, const Plan::GraphEntry& b) { return a.used < b.used; });
-      drop_graph_entry(*lru);
-      P0.graphs.erase(lru);
-    }
-    if (!P0.cap_stream) TQ_HIP(hipStreamCreateWithFlags(&P0.cap_stream, hipStreamNonBlocking));
-    TQ_HIP(hipStreamBeginCapture(P0.cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = group_enqueue(plans, n, inputs, outs, s_begin, s_end, s_step, accumulate, P0.cap_stream);
-    hipGraph_t g = nullptr;
-    const hipError_t ce = hipStreamEndCapture(P0.cap_stream, &g);
-    if (rc != TQ_OK) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    TQ_HIP(ce);
-    Plan::GraphEntry e;
-    e.key = key;
-    e.graph = g;
-    TQ_HIP(hipGraphInstantiate(&e.exec, g, nullptr, nullptr, 0));
-    TQ_HIP(hipEventCreateWithFlags(&e.done, hipEventDisableTiming));
-    P0.graphs.push_back(e);
-    hit = &P0.graphs.back();
-    ++P0.graph_builds;
-  }
-  hit->used = ++P0.graph_clock;
-  TQ_HIP(hipGraphLaunch(hit->exec, stream));
-  TQ_HIP(hipEventRecord(hit->done, stream));
-  ++P0.graph_launches;
-  return TQ_OK;
 }
 
 }  // namespace tq

@@ -1,4 +1,6 @@
-// Contraction-plan compiler and executor (host C++ over the HIP kernels).
+// Contraction-plan compiler and executor (host C++ over the HIP kernels): the Plan and the
+// functions tq_capi.cpp calls.  Implemented in tq_plan.cpp (compiler), tq_plan_exec.cpp (executor) and
+// tq_plan_run.cpp (materialize / release, graph cache, run); tq_plan_internal.h: what those share.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -278,5 +280,9 @@ int plan_run_group(Plan* const* plans, int n, const void* const* const* inputs, 
                    int64_t s_begin, int64_t s_end, int64_t s_step, int accumulate, hipStream_t stream);
 int plan_release(Plan& P);   // TQ_OK, or TQ_ERR_HIP with what is left still held (retry later)
 int plan_profile_read(Plan& P, int kind, double* ms, int64_t* launches, double* flops, double* bytes);
+// process-wide switches (tq_library_query "graphs" / "sweep"): TQ_GRAPH / TQ_SWEEP, default 1,
+// each read once per process
+bool graphs_enabled();
+bool sweeps_enabled();
 
 }  // namespace tq

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "tq_common.h"
+#include "tq_env.h"
 #include "tq_sweep.h"
 
 namespace tq {
@@ -236,10 +237,7 @@ int sweep_launch_lanes(int dtype, const SweepArgs& a, const SweepLanes& l0, hipS
   if (a.ncols == 0) return TQ_OK;
   // fan-out when every lane reads the same X and every gate fits kSweepFanKN coefficients
   // (TQ_SWEEP_FAN=0: the per-lane grid)
-  static const bool fan_on = [] {
-    const char* e = getenv("TQ_SWEEP_FAN");
-    return !(e && e[0] == '0');
-  }();
+  static const bool fan_on = env_on("TQ_SWEEP_FAN");
   SweepLanes l = l0;
   l.fan = 0;
   if (fan_on && l.n > 1 && !a.use_beta && dtype != TQ_C128) {

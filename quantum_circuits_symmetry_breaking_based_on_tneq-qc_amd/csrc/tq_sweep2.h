@@ -315,6 +315,9 @@ inline int s2d_blocks(int64_t ncols) {
   return (int)(b < 2048 ? b : 2048);
 }
 int sweepd_launch(int dtype, const S2DLaunch& L, hipStream_t stream);
+// TQ_S2D_NT=1 (default 0): dense ops store with non-temporal stores; a launch then holds one input
+// tile size (the plan executor does not mix two).  Read once per process (tq_sweepd.hip)
+bool s2d_nt_stores();
 int sweep2_timing(unsigned long long* out, int n);   // development instrumentation
 int sweep2_kclock(unsigned long long* out, int n);   // in-kernel clock records (-DTQ_KCLOCK builds)
 

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "tq_common.h"
+#include "tq_env.h"
 #include "tq_sweep2.h"
 #include "tq_kclock.h"
 
@@ -1219,10 +1220,7 @@ int launch_t(const S2Launch& L, hipStream_t stream) {
   // (r03, same box): C3 1.84 -> 1.27 ms per step (its per-slice launch of 1536 one-chunk
   // workgroups spent ~80 us per round in the store / drain phases, waves waiting 75 %), C4 +-0
   // (13.36 / 13.29 ms; 2 rounds 13.29, 4 rounds 13.24), C3 with 2 rounds 1.56 ms.
-  static const double rounds = [] {
-    const char* e = getenv("TQ_S2_CAP");
-    return e ? atof(e) : 1.0;   // resident rounds per launch (0 = no cap)
-  }();
+  static const double rounds = env_double("TQ_S2_CAP", 1.0);   // resident rounds per launch (0 = no cap)
   // per device (cached; -1 = no cap)
   static DeviceCache<1> cap_cache;
   const int cap = !(rounds > 0) ? 0 : std::max(0, cap_cache.get(0, [] {

@@ -34,6 +34,7 @@
 #include <utility>
 
 #include "tq_common.h"
+#include "tq_env.h"
 #include "tq_sweep2.h"
 
 namespace tq {
@@ -458,6 +459,11 @@ __global__ void __launch_bounds__(64 * kWaves, TQ_S2D_OCC) sweepd_kernel(S2DLaun
 
 }  // namespace
 
+bool s2d_nt_stores() {
+  static const bool v = env_opt_in("TQ_S2D_NT");
+  return v;
+}
+
 int sweepd_launch(int dtype, const S2DLaunch& L, hipStream_t stream) {
   if (dtype != TQ_C64) {
     set_error("sweepd: complex64 only");
@@ -486,14 +492,8 @@ int sweepd_launch(int dtype, const S2DLaunch& L, hipStream_t stream) {
   }
   // one round of resident workgroups over the launch's ops (the kernel strides over its tiles):
   // a second, partial round of workgroups left most CUs idle (1024 blocks on 768 slots)
-  static const bool nts = [] {
-    const char* e = getenv("TQ_S2D_NT");
-    return e && e[0] == '1';
-  }();
-  static const int order = [] {
-    const char* e = getenv("TQ_S2D_BLOCKED");
-    return e && e[0] == '1' ? 1 : 0;
-  }();
+  const bool nts = s2d_nt_stores();
+  static const int order = env_opt_in("TQ_S2D_BLOCKED") ? 1 : 0;
   if (tb > ta) std::swap(ta, tb);
   auto pow2tin = [](int t) { return t == 2 || t == 4 || t == 8 || t == 16; };
   if (!pow2tin(ta) || (tb && !pow2tin(tb))) {
@@ -541,10 +541,7 @@ int sweepd_launch(int dtype, const S2DLaunch& L, hipStream_t stream) {
   // per launch on one box), plus 16 rows' worth per column for the per-column-group work (input
   // loads, bases: 1.45 ms; 48: 1.48, -16: 1.51)
   // (TQ_S2D_SHARE=0: by products, the r04 rule, for A/B)
-  static const bool by_products = [] {
-    const char* e = getenv("TQ_S2D_SHARE");
-    return e && e[0] == '0';
-  }();
+  static const bool by_products = !env_on("TQ_S2D_SHARE");
   auto work = [&](const S2DOp& o) {
     const double c = (double)std::max<int64_t>(o.ncols, 1);
     return by_products ? c * o.tout * (8.0 + o.tin) : c * (o.tout + 16.0);

@@ -5,7 +5,7 @@ hipGraphExecDestroy / hipFree while a stream captures, so the releases are parke
 (graphs.defer_release) and run at the next call outside the capture.  Checked: the capture
 completes and replays the right values, the parked objects are released afterwards (nothing
 left); tq_plan_destroy itself reports a refused HIP release instead of ignoring it and keeps
-the plan for a retry (tq_plan.cpp plan_release)."""
+the plan for a retry (tq_plan_run.cpp plan_release)."""
 import gc
 
 import numpy as np

@@ -169,6 +169,38 @@ def test_graph_replay_matches_eager_and_rebuilds_on_new_pointers(dev):
     assert _err((part + part0).cpu().numpy(), ref) < TOL["complex64"]
 
 
+def test_graph_cache_evicts_the_least_recently_used(dev):
+    """A plan keeps at most 8 instantiated graphs: a ninth distinct output pointer evicts the least
+    recently used entry (the first), whose next execute captures again, while the latest entry is
+    replayed; every graph's result equals the eager launch sequence bit for bit."""
+    import torch
+    from tneq_qc_amd.circuits import BrickWall, amplitude_task
+    from tneq_qc_amd.expression import HipContractExpression
+    t = amplitude_task(BrickWall(14, 8, 5), list(range(4, 10)), cut=7, n_slice=3)
+    e = HipContractExpression(t.eq, *t.shapes, optimize=t.path, slices=t.sliced)
+    ts = [torch.from_numpy(np.ascontiguousarray(o)).to(dev, torch.complex64) for o in t.operands]
+    plan = e.plan(torch.complex64)
+    plan.profile(-1)                                  # profiling runs the eager launch sequence
+    eager = e(*ts)
+    plan.profile(None)
+    outs = [torch.empty(e.out_shape, dtype=torch.complex64, device=dev) for _ in range(9)]
+    b0 = plan.query("graph_builds")
+    for o in outs:
+        e(*ts, out=o)
+    assert plan.query("graph_builds") == b0 + 9
+    got = [o.clone() for o in outs]
+    outs[0].zero_()
+    e(*ts, out=outs[0])                               # evicted by the ninth: captured again
+    assert plan.query("graph_builds") == b0 + 10
+    got.append(outs[0].clone())
+    outs[8].zero_()
+    e(*ts, out=outs[8])                               # still cached: replayed
+    assert plan.query("graph_builds") == b0 + 10
+    got.append(outs[8].clone())
+    for g in got:
+        assert torch.equal(g, eager)
+
+
 @pytest.mark.parametrize("dtype", ["complex64", "complex128", "float32", "float64"])
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
 def test_fused_sweep_chains_random(dev, dtype, seed):

@@ -109,3 +109,40 @@ def test_run_group_refuses_mismatched_members(dev):
     for o, (a, b) in ((o1, x), (o2, y)):
         ref = (a @ b).cpu().numpy()
         assert np.abs(o.cpu().numpy() - ref).max() <= 1e-5 * np.abs(ref).max()
+
+
+def test_group_graph_is_cached_in_the_leader(dev):
+    """A group execute is one hipGraph cached in its first plan under every member's buffers: the
+    same call again replays it, other output buffers capture a new one, the other members hold no
+    graph; the replay equals the eager group run bit for bit."""
+    import torch
+    from tneq_qc_amd.expression import HipContractExpression, run_group
+    rng = np.random.default_rng(1)
+
+    def ops(shapes):
+        return [torch.tensor(rng.standard_normal(s) + 1j * rng.standard_normal(s), dtype=torch.complex64,
+                             device=dev) for s in shapes]
+    e1 = HipContractExpression("ab,bc->ac", (8, 16), (16, 4))
+    m1 = e1.bind(*ops([(8, 16), (16, 4)]), private_plan=True)
+    m2 = e1.bind(*ops([(8, 16), (16, 4)]), private_plan=True)
+    o1, o2 = m1.new_out(), m2.new_out()
+    b0, l0 = m1.plan.query("graph_builds"), m1.plan.query("graph_launches")
+    run_group([m1, m2], [o1, o2])
+    run_group([m1, m2], [o1, o2])
+    assert m1.plan.query("graph_builds") == b0 + 1
+    assert m1.plan.query("graph_launches") == l0 + 2
+    assert m2.plan.query("graph_builds") == 0
+    torch.cuda.synchronize()
+    g1, g2 = o1.clone(), o2.clone()
+    m1.plan.set("graph", 0)                          # the same group run, launched eagerly
+    r1, r2 = m1.new_out(), m2.new_out()
+    run_group([m1, m2], [r1, r2])
+    m1.plan.set("graph", 1)
+    torch.cuda.synchronize()
+    assert m1.plan.query("graph_builds") == b0 + 1
+    assert torch.equal(g1, r1) and torch.equal(g2, r2)
+    run_group([m1, m2], [o2, o1])                    # swapped output buffers: another graph
+    assert m1.plan.query("graph_builds") == b0 + 2
+    assert m2.plan.query("graph_builds") == 0
+    torch.cuda.synchronize()
+    assert torch.equal(o2, r1) and torch.equal(o1, r2)
