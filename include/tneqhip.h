@@ -176,7 +176,18 @@ int tq_plan_clone(tq_plan src, tq_plan* out);
  * "s2_programs" = 1 (default, env TQ_S2_PROG) runs the sweep2 register-block passes whose gate
  * sequence is in the kernel's program set as straight-line pass programs, 0 all of them on the
  * per-gate interpreter (no recompile; queries "n_s2_prog_gate_work" / "n_s2_block_gate_work":
- * gate work under programs / of all block passes, "n_s2_prog_passes_<id>", "n_s2_programs"). */
+ * gate work under programs / of all block passes, "n_s2_prog_passes_<id>", "n_s2_programs");
+ * "fold_slices" = 1 (default, env TQ_FOLD_SLICES): a plan with sliced modes also holds the same
+ * network compiled with no sliced modes (the whole program), and an execute call over every
+ * slice (begin 0, end n_slices, step 1) runs that instead of the slice lanes when it moves no
+ * more bytes, does no more flops and needs no more arena than the sliced program and the
+ * per-slice part holds no GEMM (tq_plan_execute_group: when that holds for every member); 0
+ * always runs the slice lanes (queries "fold_slices": such a
+ * call will fold, "whole_bytes_moved" / "whole_flops" / "whole_arena_bytes" / "whole_n_launch" /
+ * "whole_n_s2_block_gate_work" / "whole_n_s2_prog_gate_work": the whole program's costs,
+ * "folded_executes": calls it ran, "resident_arena_bytes" / "whole_resident_arena_bytes": arena
+ * held on the device by either program -- each takes its memory at its first use; every other
+ * key describes the sliced program). */
 int tq_plan_set(tq_plan plan, const char* key, int64_t value);
 /* human-readable per-step description into buf (for debugging / DESIGN evidence) */
 int tq_plan_describe(tq_plan plan, char* buf, size_t n);

@@ -300,6 +300,14 @@ int tq_plan_set(tq_plan p, const char* key, int64_t value) {
     return tq::plan_recompile(p->plan, p->plan.group_hint, (int)value);
     TQ_GUARD_END
   }
+  if (k == "fold_slices") {      // 0: a call over every slice runs the slice lanes, not the whole program
+    if (p->materialized) {
+      tq::set_error("tq_plan_set: fold_slices before the plan's first execute only");
+      return TQ_ERR_INVALID;
+    }
+    p->plan.use_fold = value != 0;
+    return TQ_OK;
+  }
   if (k == "sweep_coop") {       // 0: the multi-chunk sweep2 levels of a chain run one launch each
     p->plan.use_coop = value != 0;
     return TQ_OK;
@@ -387,6 +395,25 @@ int64_t tq_plan_query(tq_plan p, const char* key) {
   if (k == "n_s2_block_gate_work") return tq::plan_s2_gate_work(P, false);
   if (k == "n_s2_prog_gate_work") return tq::plan_s2_gate_work(P, true);
   if (k == "out_numel") return P.out_numel;
+  // the whole program (Plan::whole): will a call over every slice run it; its costs; calls it ran
+  if (k == "fold_slices") return tq::plan_folds(P, 0, P.n_slices, 1) ? 1 : 0;
+  if (k == "folded_executes") return P.folded_executes;
+  if (k == "resident_arena_bytes") return P.d_arena ? (int64_t)P.arena_bytes : 0;
+  if (k.rfind("whole_", 0) == 0) {
+    if (!P.whole) return -1;
+    const tq::Plan& W = *P.whole;
+    if (k == "whole_bytes_moved") return (int64_t)W.bytes;
+    if (k == "whole_flops") return (int64_t)W.flops;
+    if (k == "whole_arena_bytes") return (int64_t)W.arena_bytes;
+    if (k == "whole_resident_arena_bytes") return W.d_arena ? (int64_t)W.arena_bytes : 0;
+    if (k == "whole_n_launch") {   // launches as executed (chain launches merged)
+      int64_t c = W.n_launch_once + W.n_launch_slice;
+      if (P.use_seq) for (auto& r : W.seq_once) c -= r.second - r.first - 1;
+      return c;
+    }
+    if (k == "whole_n_s2_block_gate_work") return tq::plan_s2_gate_work(W, false);
+    if (k == "whole_n_s2_prog_gate_work") return tq::plan_s2_gate_work(W, true);
+  }
   return -1;
 }
 
@@ -405,10 +432,10 @@ int tq_plan_execute(tq_plan p, const void* const* inputs, void* out, int64_t sli
                     int64_t slice_end, int64_t slice_step, int accumulate, void* stream) {
   TQ_GUARD_BEGIN
   TQ_CHECK_ARG(p != nullptr, "null plan");
-  if (!p->materialized) {  // device memory is taken at first use, so plans compile without a GPU
-    TQ_TRY(tq::plan_materialize(p->plan, nullptr, nullptr, (hipStream_t)stream));
-    p->materialized = true;
-  }
+  // device memory is taken at first use, so plans compile without a GPU: that of the program
+  // this call runs (the slice lanes, or the whole program of a call over every slice)
+  TQ_TRY(tq::plan_prepare(p->plan, slice_begin, slice_end, slice_step, (hipStream_t)stream));
+  p->materialized = true;
   trace("execute", p, (int64_t)(intptr_t)stream);
   const int rc = tq::plan_run(p->plan, inputs, out, slice_begin, slice_end, slice_step, accumulate,
                               (hipStream_t)stream);
@@ -425,12 +452,10 @@ int tq_plan_execute_group(int n, const tq_plan* plans, const void* const* const*
   std::vector<tq::Plan*> ps((size_t)n);
   for (int k = 0; k < n; ++k) {
     TQ_CHECK_ARG(plans[k] != nullptr && inputs[k] != nullptr, "null plan / inputs in a group");
-    if (!plans[k]->materialized) {
-      TQ_TRY(tq::plan_materialize(plans[k]->plan, nullptr, nullptr, (hipStream_t)stream));
-      plans[k]->materialized = true;
-    }
     ps[k] = &plans[k]->plan;
   }
+  TQ_TRY(tq::plan_prepare_group(ps.data(), n, slice_begin, slice_end, slice_step, (hipStream_t)stream));
+  for (int k = 0; k < n; ++k) plans[k]->materialized = true;
   trace("execute_group", plans[0], n);
   const int rc = tq::plan_run_group(ps.data(), n, inputs, outs, slice_begin, slice_end, slice_step, accumulate,
                                     (hipStream_t)stream);
@@ -442,10 +467,7 @@ int tq_plan_execute_group(int n, const tq_plan* plans, const void* const* const*
 int tq_plan_profile(tq_plan p, int enable) {
   TQ_GUARD_BEGIN
   TQ_CHECK_ARG(p != nullptr, "null plan");
-  tq::Plan& P = p->plan;
-  for (auto& ev : P.ev_used) P.ev_free.push_back(ev);  // reset: recycle recorded events
-  P.ev_used.clear();
-  P.profile = (unsigned)enable;
+  tq::plan_profile_set(p->plan, (unsigned)enable);
   return TQ_OK;
   TQ_GUARD_END
 }

@@ -2693,6 +2693,21 @@ int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, cons
   P.min_chunks = min_chunks;
   static const bool prog_default = env_on("TQ_S2_PROG");   // TQ_S2_PROG=0: every block pass on the interpreter
   plan_s2_programs(P, prog_default);
+  P.use_fold = fold_slices_enabled();
+  if (n_sliced > 0) {
+    // the whole program: the same network and path with no sliced modes (Plan::whole).  Eligible
+    // by cost only: nothing it needs may exceed the sliced program's, and the sliced program's
+    // per-slice part holds no GEMM (folding a sliced leg into a GEMM's K changes its f16-split
+    // rounding, which the parity bounds pin)
+    auto W = std::make_shared<Plan>();
+    if (plan_compile(*W, dtype, n_inputs, in_ranks, in_modes, in_extents, in_strides, out_rank, out_modes,
+                     n_steps, path, 0, nullptr, group_hint, min_chunks) == TQ_OK) {
+      bool slice_gemm = false;
+      for (const Op& op : P.ops) slice_gemm = slice_gemm || (op.kind == OP_GEMM && !op.invariant);
+      P.fold_ok = !slice_gemm && W->bytes <= P.bytes && W->flops <= P.flops && W->arena_bytes <= P.arena_bytes;
+      P.whole = std::move(W);
+    }
+  }
   return TQ_OK;
 }
 
@@ -2722,6 +2737,7 @@ void plan_s2_programs(Plan& P, bool on) {
       pm[kS2PmB] = B | (on ? s2_prog_bits(B, pm + kS2PmCode, pm[kS2PmCount] & 0xff) : 0);
     }
   });
+  if (P.whole) plan_s2_programs(*P.whole, on);
 }
 
 int64_t plan_s2_prog_passes(const Plan& P, int id) {
@@ -2771,7 +2787,7 @@ int plan_recompile(Plan& P, int group_hint, int min_chunks) {
   if (group_hint == P.group_hint && min_chunks == P.min_chunks) return TQ_OK;
   const CompileArgs a = P.args;
   const bool seq = P.use_seq, coop = P.use_coop, planes = P.use_planes, graph = P.use_graph;
-  const bool prog = P.use_s2_prog;
+  const bool prog = P.use_s2_prog, fold = P.use_fold;
   Plan Q;
   TQ_TRY(plan_compile(Q, P.dtype, (int)a.in_ranks.size(), a.in_ranks.data(), a.in_modes.data(),
                       a.in_extents.data(), a.in_strides.empty() ? nullptr : a.in_strides.data(),
@@ -2781,6 +2797,7 @@ int plan_recompile(Plan& P, int group_hint, int min_chunks) {
   Q.use_coop = coop;
   Q.use_planes = planes;
   Q.use_graph = graph;
+  Q.use_fold = fold;
   plan_s2_programs(Q, prog);
   P = std::move(Q);
   return TQ_OK;
@@ -2804,6 +2821,12 @@ void plan_clone_compiled(const Plan& src, Plan& dst) {
   dst.graph_builds = dst.graph_launches = 0;
   dst.ps_fallbacks = 0;
   dst.run_mode = 0;
+  dst.resident = dst.fold_failed = false;
+  dst.folded_executes = 0;
+  if (src.whole) {
+    dst.whole = std::make_shared<Plan>();
+    plan_clone_compiled(*src.whole, *dst.whole);
+  }
 }
 
 void plan_planes_layout(Plan& P) {

@@ -3,6 +3,7 @@
 // tq_plan_run.cpp (materialize / release, graph cache, run); tq_plan_internal.h: what those share.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -211,6 +212,18 @@ struct Plan {
   // pass programs of the sweep2 block passes (tq_sweep2.h kS2Progs): env TQ_S2_PROG, default 1;
   // tq_plan_set "s2_programs" (plan_s2_programs, before the first execute)
   bool use_s2_prog = true;
+  // the whole program (plans compiled with sliced modes only): the same network and path compiled
+  // with no sliced modes, owned by this plan.  An execute call that covers every slice runs it
+  // instead of the slice lanes (plan_folds) when it is eligible (fold_ok: it moves no more bytes,
+  // does no more flops and needs no more arena than the sliced program, and the sliced program's
+  // per-slice part holds no GEMM) and the option is on (env TQ_FOLD_SLICES, default 1;
+  // tq_plan_set "fold_slices").  It has its own arena and tables, taken at its first use
+  // (plan_prepare); its graphs and counters live in this plan.
+  std::shared_ptr<Plan> whole;
+  bool fold_ok = false, use_fold = true;
+  bool fold_failed = false;   // the whole program's memory could not be taken: lanes path for good
+  bool resident = false;      // plan_materialize has run for this program
+  int64_t folded_executes = 0;
   std::string describe;
   // hipGraph of the whole launch sequence of one execute call, replayed while the call's
   // pointers / slice range / flags are unchanged (a plan is hundreds of small launches)
@@ -223,11 +236,12 @@ struct Plan {
     int planes = 0; // the pre-split boundary GEMM was on
     bool seq = true;  // Plan::use_seq
     bool coop = false;  // Plan::use_coop
+    int prog = 0;   // 1: the call ran the whole program (Plan::whole)
     // a group execute (plan_run_group): every member's output and serial
     std::vector<const void*> group;
     bool operator==(const GraphKey& o) const {
       return inputs == o.inputs && out == o.out && b == o.b && e == o.e && s == o.s && acc == o.acc &&
-             mode == o.mode && seq == o.seq && coop == o.coop && planes == o.planes && group == o.group;
+             mode == o.mode && seq == o.seq && coop == o.coop && planes == o.planes && prog == o.prog && group == o.group;
     }
   };
   bool use_graph = true;
@@ -271,6 +285,15 @@ void plan_clone_compiled(const Plan& src, Plan& dst);
 void plan_planes_layout(Plan& P);
 // upload tables / allocate arena (owned) — or use caller memory when `arena`/`tables` are given
 int plan_materialize(Plan& P, void* arena, void* tables, hipStream_t stream);
+// an execute call over [s_begin, s_end) by s_step runs the plan's whole program
+bool plan_folds(const Plan& P, int64_t s_begin, int64_t s_end, int64_t s_step);
+// before an execute call (and before any capture): device memory of the program the call runs,
+// at that program's first use; a whole program whose memory cannot be taken is given up for good
+int plan_prepare(Plan& P, int64_t s_begin, int64_t s_end, int64_t s_step, hipStream_t stream);
+// ... of a group execute: the whole programs when every member folds, else every member's lanes
+int plan_prepare_group(Plan* const* plans, int n, int64_t s_begin, int64_t s_end, int64_t s_step, hipStream_t stream);
+// profiling mask of the plan (and its whole program); resets the recorded events
+void plan_profile_set(Plan& P, unsigned mask);
 int plan_run(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
              int64_t s_step, int accumulate, hipStream_t stream);
 // a group of plans compiled from the same network, run in lockstep on one stream: every sweep2 /

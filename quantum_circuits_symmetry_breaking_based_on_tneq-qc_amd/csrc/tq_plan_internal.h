@@ -75,6 +75,9 @@ inline bool s2_enabled() { static const bool v = env_on("TQ_SWEEP2"); return v; 
 inline bool s2_dense_enabled() { static const bool v = env_on("TQ_S2_DENSE"); return v; }
 // the pre-split boundary GEMM (TQ_GEMM_PLANES=0: the GEMM-side split kernel instead)
 inline bool planes_enabled() { static const bool v = env_on("TQ_GEMM_PLANES"); return v; }
+// TQ_FOLD_SLICES=0: an execute call that covers every slice runs the slice lanes all the same
+// (default 1: the plan's whole program, Plan::whole; tq_plan_set "fold_slices" per plan)
+inline bool fold_slices_enabled() { static const bool v = env_on("TQ_FOLD_SLICES"); return v; }
 // TQ_S2_REORDER (default 1): commute a chain's square gates into fuller register blocks
 inline bool s2_reorder_on() { static const bool v = env_on("TQ_S2_REORDER"); return v; }
 // TQ_SKINNY_STRIDED=0: tiny-output GEMM steps permute their operands like any other

@@ -2,6 +2,9 @@
 //   * plan_materialize uploads the tables and allocates the arena (or takes the caller's),
 //     plan_release frees what the plan holds (retryable: nothing is forgotten before its release
 //     succeeded), plan_profile_read sums the executor's event records;
+//   * plan_prepare takes the device memory of the program an execute call runs -- the slice lanes,
+//     or the plan's whole program (Plan::whole) when the call covers every slice (plan_folds) --
+//     at that program's first use;
 //   * plan_run checks the call, picks the pre-split mode, runs the call (plan_launch) and re-runs
 //     the slices whose pre-split scale window was missed; plan_run_group does the same for a
 //     lockstep group of plans compiled from one network;
@@ -19,7 +22,7 @@ namespace tq {
 
 int plan_materialize(Plan& P, void* arena, void* tables, hipStream_t stream) {
   TQ_HIP(hipGetDevice(&P.device));
-  P.serial = next_plan_serial();
+  if (!P.serial) P.serial = next_plan_serial();
   if (arena || tables) {
     P.d_arena = arena;
     P.d_tables = tables;
@@ -49,19 +52,70 @@ int plan_materialize(Plan& P, void* arena, void* tables, hipStream_t stream) {
       P.d_planes = nullptr;   // no room: the GEMM-side split path runs instead
     }
   }
+  P.resident = true;
   return TQ_OK;
+}
+
+bool plan_folds(const Plan& P, int64_t s_begin, int64_t s_end, int64_t s_step) {
+  // (cooperative chain launches, opt-in and checked after the call, stay with the slice lanes)
+  return P.whole && P.fold_ok && P.use_fold && !P.fold_failed && !P.use_coop && s_begin == 0 &&
+         s_end == P.n_slices && s_step == 1;
+}
+
+int plan_prepare(Plan& P, int64_t s_begin, int64_t s_end, int64_t s_step, hipStream_t stream) {
+  if (P.device < 0) TQ_HIP(hipGetDevice(&P.device));
+  if (!P.serial) P.serial = next_plan_serial();
+  if (plan_folds(P, s_begin, s_end, s_step)) {
+    Plan& W = *P.whole;
+    if (W.resident) return TQ_OK;
+    if (plan_materialize(W, nullptr, nullptr, stream) == TQ_OK) return TQ_OK;
+    // no room for the whole program: what it took is given back and the plan keeps to the slice
+    // lanes for good (like a missing d_planes keeps the GEMM-side split path)
+    (void)hipGetLastError();
+    (void)plan_release(W);
+    P.fold_failed = true;
+  }
+  if (!P.resident) TQ_TRY(plan_materialize(P, nullptr, nullptr, stream));
+  return TQ_OK;
+}
+
+int plan_prepare_group(Plan* const* plans, int n, int64_t s_begin, int64_t s_end, int64_t s_step, hipStream_t stream) {
+  // a group folds when every member does; one member without its whole program puts all on the lanes
+  bool fold = true;
+  for (int k = 0; k < n; ++k) fold = fold && plan_folds(*plans[k], s_begin, s_end, s_step);
+  if (fold) {
+    for (int k = 0; k < n; ++k) TQ_TRY(plan_prepare(*plans[k], s_begin, s_end, s_step, stream));
+    for (int k = 0; k < n; ++k) fold = fold && plan_folds(*plans[k], s_begin, s_end, s_step);
+    if (fold) return TQ_OK;
+  }
+  for (int k = 0; k < n; ++k)
+    if (!plans[k]->resident) TQ_TRY(plan_materialize(*plans[k], nullptr, nullptr, stream));
+  return TQ_OK;
+}
+
+void plan_profile_set(Plan& P, unsigned mask) {
+  for (Plan* q : {&P, P.whole.get()}) {
+    if (!q) continue;
+    for (auto& ev : q->ev_used) q->ev_free.push_back(ev);  // reset: recycle recorded events
+    q->ev_used.clear();
+    q->profile = mask;
+  }
 }
 
 int plan_profile_read(Plan& P, int kind, double* ms, int64_t* launches, double* flops,
                       double* bytes) {
   double t = 0, f = 0, b = 0;
   int64_t n = 0;
-  for (auto& ev : P.ev_used) {
-    if (kind >= 0 && ev.kind != kind) continue;
-    TQ_HIP(hipEventSynchronize(ev.b));
-    float e = 0;
-    TQ_HIP(hipEventElapsedTime(&e, ev.a, ev.b));
-    t += e; f += ev.flops; b += ev.bytes; ++n;
+  // (a folded call's records are the whole program's)
+  for (Plan* q : {&P, P.whole.get()}) {
+    if (!q) continue;
+    for (auto& ev : q->ev_used) {
+      if (kind >= 0 && ev.kind != kind) continue;
+      TQ_HIP(hipEventSynchronize(ev.b));
+      float e = 0;
+      TQ_HIP(hipEventElapsedTime(&e, ev.a, ev.b));
+      t += e; f += ev.flops; b += ev.bytes; ++n;
+    }
   }
   if (ms) *ms = t;
   if (launches) *launches = n;
@@ -172,10 +226,12 @@ int graph_run(Plan& P, const Plan::GraphKey& key, hipStream_t stream, Enqueue&& 
   return TQ_OK;
 }
 
-// one execute call of one plan: eagerly, or as the replay of its hipGraph
-int plan_launch(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
+// one execute call of one plan: eagerly, or as the replay of its hipGraph.  W: the plan's whole
+// program when the call runs it (its one "slice" is the sum over every slice); the graph is P's
+int plan_launch(Plan& P, Plan* W, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
                 int64_t s_step, int accumulate, hipStream_t stream) {
   auto enqueue = [&](hipStream_t s) {
+    if (W) return plan_enqueue(*W, inputs, out, 0, 1, 1, accumulate, s);
     return plan_enqueue(P, inputs, out, s_begin, s_end, s_step, accumulate, s);
   };
   bool eager = true;
@@ -185,9 +241,10 @@ int plan_launch(Plan& P, const void* const* inputs, void* out, int64_t s_begin, 
   key.inputs.assign(inputs, inputs + P.n_inputs);
   key.out = out; key.b = s_begin; key.e = s_end; key.s = s_step; key.acc = accumulate;
   key.mode = P.run_mode;
-  key.planes = planes_active(P) ? 1 : 0;
+  key.planes = planes_active(W ? *W : P) ? 1 : 0;
   key.seq = P.use_seq;
   key.coop = P.use_coop;
+  key.prog = W ? 1 : 0;
   return graph_run(P, key, stream, enqueue);
 }
 
@@ -210,6 +267,8 @@ bool same_structure(const Plan& a, const Plan& b) {
 
 int plan_release(Plan& P) {
   int rc = drop_graph(P);
+  // the whole program's memory: after this plan's graphs (which address it) have finished
+  if (P.whole && rc == TQ_OK) rc = plan_release(*P.whole);
   if (P.cap_stream && rel(hipStreamDestroy(P.cap_stream), "capture stream", rc)) P.cap_stream = nullptr;
   auto drop_events = [&](std::vector<Plan::Ev>& v) {
     std::vector<Plan::Ev> keep;
@@ -240,6 +299,7 @@ int plan_release(Plan& P) {
   }
   if (P.h_bad && rel(hipHostFree(P.h_bad), "host flag", rc)) P.h_bad = nullptr;
   if (P.d_planes && rel(hipFree(P.d_planes), "planes", rc)) P.d_planes = nullptr;
+  if (!P.d_arena && !P.d_tables) P.resident = false;
   return rc;
 }
 
@@ -247,7 +307,9 @@ int plan_run(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int
              int64_t s_step, int accumulate, hipStream_t stream) {
   TQ_CHECK_ARG(s_step >= 1, "slice_step");
   TQ_CHECK_ARG(s_begin >= 0 && s_end <= P.n_slices, "slice range");
-  TQ_CHECK_ARG(P.arena_bytes == 0 || P.d_arena, "plan not materialized");
+  // the whole program runs a call over every slice once its memory is there (plan_prepare)
+  Plan* W = plan_folds(P, s_begin, s_end, s_step) && P.whole->resident ? P.whole.get() : nullptr;
+  TQ_CHECK_ARG(W ? (W->arena_bytes == 0 || W->d_arena) : (P.arena_bytes == 0 || P.d_arena), "plan not materialized");
   {
     // a plan's arena, tables and graphs live on one device; running it with another device
     // current would hand that device foreign pointers
@@ -261,6 +323,17 @@ int plan_run(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int
   // under the current library switches, and the stream is not being captured by the caller
   // (the window check below synchronizes)
   P.run_mode = 0;
+  if (W) {
+    // the per-plan options follow the parent; no pre-split (predicted-scale) GEMM mode
+    W->use_seq = P.use_seq;
+    W->use_planes = P.use_planes;
+    W->use_coop = false;
+    W->profile = P.profile;
+    W->run_mode = 0;
+    TQ_TRY(plan_launch(P, W, inputs, out, s_begin, s_end, s_step, accumulate, stream));
+    ++P.folded_executes;
+    return TQ_OK;
+  }
   if (P.n_ps && P.h_bad) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     TQ_HIP(hipStreamIsCapturing(stream, &cs));
@@ -270,7 +343,7 @@ int plan_run(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int
         ok = false;
     P.run_mode = ok ? 1 : 0;
   }
-  TQ_TRY(plan_launch(P, inputs, out, s_begin, s_end, s_step, accumulate, stream));
+  TQ_TRY(plan_launch(P, nullptr, inputs, out, s_begin, s_end, s_step, accumulate, stream));
   if (P.use_coop && !P.coop_once.empty() && P.d_tables) {
     // cooperative chain launches (opt-in) rely on their workgroups being co-resident; a wait
     // that gave up (sync[1], counted by the kernel) means the op read stale data: the execute
@@ -328,19 +401,36 @@ int plan_run_group(Plan* const* plans, int n, const void* const* const* inputs, 
   TQ_CHECK_ARG(s_begin >= 0 && s_end <= P0.n_slices, "slice range");
   int cur = -1;
   TQ_HIP(hipGetDevice(&cur));
+  // every member's whole program (a call over every slice, each one's memory there), or the lanes
+  bool fold = true;
+  for (int k = 0; k < n; ++k)
+    fold = fold && plan_folds(*plans[k], s_begin, s_end, s_step) && plans[k]->whole->resident;
+  std::vector<Plan*> run(plans, plans + n);
   for (int k = 0; k < n; ++k) {
     Plan& P = *plans[k];
-    TQ_CHECK_ARG(P.arena_bytes == 0 || P.d_arena, "plan not materialized");
+    if (fold) {
+      Plan& W = *P.whole;
+      W.use_seq = P.use_seq;
+      W.use_planes = P.use_planes;
+      W.use_coop = false;
+      W.profile = P.profile;
+      run[k] = &W;
+    }
+    TQ_CHECK_ARG(run[k]->arena_bytes == 0 || run[k]->d_arena, "plan not materialized");
     TQ_CHECK_ARG(P.device < 0 || cur == P.device, "a group plan was materialized on another device");
     for (int q = 0; q < k; ++q)
       TQ_CHECK_ARG(plans[q] != plans[k] && outs[q] != outs[k], "a group runs distinct plans into distinct outputs");
-    P.run_mode = 0;   // no pre-split (predicted-scale) GEMM mode in a group
-    TQ_CHECK_ARG(same_structure(P0, P), "the plans of a group must be compiled from the same network");
+    P.run_mode = run[k]->run_mode = 0;   // no pre-split (predicted-scale) GEMM mode in a group
+    TQ_CHECK_ARG(same_structure(P0, P) && same_structure(*run[0], *run[k]),
+                 "the plans of a group must be compiled from the same network");
   }
   TQ_CHECK_ARG(!P0.use_coop, "cooperative chain launches do not run in a group");
   auto enqueue = [&](hipStream_t s) {
+    if (fold) return group_enqueue(run.data(), n, inputs, outs, 0, 1, 1, accumulate, s);
     return group_enqueue(plans, n, inputs, outs, s_begin, s_end, s_step, accumulate, s);
   };
+  if (fold)
+    for (int k = 0; k < n; ++k) ++plans[k]->folded_executes;
   bool eager = true;
   TQ_TRY(run_eagerly(P0, stream, &eager));
   if (eager) return enqueue(stream);
@@ -353,8 +443,9 @@ int plan_run_group(Plan* const* plans, int n, const void* const* const* inputs, 
     key.group.push_back(reinterpret_cast<const void*>((uintptr_t)plans[k]->serial));
   }
   key.out = outs[0]; key.b = s_begin; key.e = s_end; key.s = s_step; key.acc = accumulate;
-  key.planes = planes_active(P0) ? 1 : 0;
+  key.planes = planes_active(*run[0]) ? 1 : 0;
   key.seq = P0.use_seq;
+  key.prog = fold ? 1 : 0;
   return graph_run(P0, key, stream, enqueue);
 }
 

@@ -73,7 +73,9 @@ class NativePlan:
         "sweep_chain" (chain launches of small dependent sweep2 ops, default 1), "sweep_coop"
         (cooperative launches of dependent multi-chunk sweep2 levels, default 0 = TQ_S2_COOP;
         diagnostic, measured slower), "s2_programs" (sweep2 block passes as compile-time pass
-        programs, default 1 = TQ_S2_PROG; before the first execute)."""
+        programs, default 1 = TQ_S2_PROG; before the first execute), "fold_slices" (a call over
+        every slice runs the plan's whole program instead of the slice lanes when that costs no
+        more, default 1 = TQ_FOLD_SLICES; before the first execute)."""
         check(_lib.lib().tq_plan_set(self._h, key.encode(), int(value)), "tq_plan_set")
 
     def describe(self) -> str:

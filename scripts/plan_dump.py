@@ -25,6 +25,12 @@ KEYS = (
     "planes_bytes", "planes_ws_bytes", "planes_gemm_M", "planes_gemm_N", "planes_gemm_K", "planes_gemm_lda",
     "planes_gemm_ldb", "s2_programs", "n_s2_programs", "n_s2_block_gate_work", "n_s2_prog_gate_work",
 )
+# the whole program of a plan with sliced modes (what a call over every slice runs when fold_slices
+# is 1); printed last, so the lines above stay comparable with builds that lack these keys
+WHOLE_KEYS = (
+    "fold_slices", "whole_bytes_moved", "whole_flops", "whole_arena_bytes", "whole_n_launch",
+    "whole_n_s2_block_gate_work", "whole_n_s2_prog_gate_work",
+)
 
 
 def main() -> None:
@@ -54,6 +60,8 @@ def main() -> None:
         print(f"{key} = {plan.query(key)}")
     for i in range(1, plan.query("n_s2_programs") + 1):
         print(f"n_s2_prog_passes_{i} = {plan.query(f'n_s2_prog_passes_{i}')}")
+    for key in WHOLE_KEYS:
+        print(f"{key} = {plan.query(key)}")
 
 
 if __name__ == "__main__":
