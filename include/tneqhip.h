@@ -189,6 +189,27 @@ int tq_plan_clone(tq_plan src, tq_plan* out);
  * held on the device by either program -- each takes its memory at its first use; every other
  * key describes the sliced program). */
 int tq_plan_set(tq_plan plan, const char* key, int64_t value);
+/* Declares which inputs are VOLATILE: the ones whose contents may change between two execute
+ * calls (n ids; n < 0 restores the default, every input).  Before the plan's first execute, like
+ * "group_hint" / "min_chunks" (the plan is compiled again; clones made afterwards inherit it).
+ * Every step of the path whose subtree holds no volatile and no sliced input is FROZEN: the plan
+ * computes it in the first execute call and keeps what later steps read; the calls after that run
+ * the rest only.  The frozen results are computed again when
+ *   - a non-volatile input's POINTER differs from the one they were computed from,
+ *   - tq_plan_set(plan, "frozen_valid", 0) was called -- the caller's duty after writing into a
+ *     non-volatile operand in place: the plan cannot see that,
+ *   - the previous execute call returned an error, or the plan was released.
+ * A call on another stream than the one that computed them waits for them first.  A call enqueued
+ * into the caller's stream capture always runs everything and leaves this state alone (replaying
+ * that capture recomputes the frozen results from the capture's own pointers).  A group execute
+ * skips the frozen part only when every member's results are valid.
+ * Queries: "n_ops_frozen", "n_launch_frozen" (launches a call that computes them adds to one that
+ * does not: levels of the two parts that do not depend on each other share a launch),
+ * "bytes_frozen", "flops_frozen" (the frozen part;
+ * "n_ops_once", "n_launch_once", "bytes_once", "flops_once" count the rest of the hoisted part),
+ * "frozen_kept_bytes" (results kept for the later steps), "frozen_valid", "frozen_runs" (execute
+ * calls that computed them), and their "whole_" twins for the whole program. */
+int tq_plan_set_volatile(tq_plan plan, int n, const int32_t* input_ids);
 /* human-readable per-step description into buf (for debugging / DESIGN evidence) */
 int tq_plan_describe(tq_plan plan, char* buf, size_t n);
 

@@ -308,6 +308,14 @@ int tq_plan_set(tq_plan p, const char* key, int64_t value) {
     p->plan.use_fold = value != 0;
     return TQ_OK;
   }
+  if (k == "frozen_valid") {     // 0: the next execute call computes the frozen results again
+    if (value != 0) {
+      tq::set_error("tq_plan_set: frozen_valid takes 0 only (an execute call makes the results valid)");
+      return TQ_ERR_INVALID;
+    }
+    tq::plan_frozen_invalidate(p->plan);
+    return TQ_OK;
+  }
   if (k == "sweep_coop") {       // 0: the multi-chunk sweep2 levels of a chain run one launch each
     p->plan.use_coop = value != 0;
     return TQ_OK;
@@ -324,10 +332,40 @@ int tq_plan_set(tq_plan p, const char* key, int64_t value) {
   return TQ_ERR_INVALID;
 }
 
+int tq_plan_set_volatile(tq_plan p, int n, const int32_t* input_ids) {
+  TQ_GUARD_BEGIN
+  TQ_CHECK_ARG(p != nullptr, "null plan");
+  TQ_CHECK_ARG(!p->materialized, "tq_plan_set_volatile: before the plan's first execute only");
+  return tq::plan_set_volatile(p->plan, n, input_ids);
+  TQ_GUARD_END
+}
+
+// launches of schedule entries [b, e) of sched_once as executed (chain launches merged)
+static int64_t launches_in(const tq::Plan& P, bool seq, bool coop, int b, int e) {
+  int64_t c = e - b;
+  if (seq) for (auto& r : P.seq_once) if (r.first >= b && r.second <= e) c -= r.second - r.first - 1;
+  if (coop) for (auto& r : P.coop_once) if (r.first >= b && r.second <= e) c -= r.second - r.first - 1;
+  return c;
+}
+
+// the frozen part of one program (tq_plan_set_volatile): key without its "whole_" prefix
+static int64_t frozen_query(const tq::Plan& R, bool seq, bool coop, const std::string& k) {
+  if (k == "n_ops_frozen") { int64_t c = 0; for (auto& o : R.ops) c += o.frozen; return c; }
+  // what a full run launches on top of a live-only one (levels that share a launch counted once)
+  if (k == "n_launch_frozen") return launches_in(R, seq, coop, 0, R.n_sched_frozen) - R.n_full_merged;
+  if (k == "bytes_frozen") return (int64_t)R.bytes_frozen;
+  if (k == "flops_frozen") return (int64_t)R.flops_frozen;
+  if (k == "frozen_kept_bytes") return (int64_t)R.frozen_kept_bytes;
+  if (k == "frozen_valid") return R.n_sched_frozen > 0 && R.frozen_valid ? 1 : 0;
+  if (k == "frozen_runs") return R.frozen_runs;
+  return -2;
+}
+
 int64_t tq_plan_query(tq_plan p, const char* key) {
   if (!p || !key) return -1;
   const tq::Plan& P = p->plan;
   const std::string k(key);
+  if (const int64_t v = frozen_query(P, P.use_seq, P.use_coop, k); v != -2) return v;
   if (k == "n_slices") return P.n_slices;
   if (k == "arena_bytes") return (int64_t)P.arena_bytes;
   if (k == "table_bytes") return (int64_t)P.table_bytes;
@@ -337,7 +375,7 @@ int64_t tq_plan_query(tq_plan p, const char* key) {
   if (k == "flops_slice") return (int64_t)P.flops_slice;
   if (k == "bytes_once") return (int64_t)P.bytes_once;
   if (k == "bytes_slice") return (int64_t)P.bytes_slice;
-  if (k == "n_ops_once") { int64_t c = 0; for (auto& o : P.ops) c += o.invariant; return c; }
+  if (k == "n_ops_once") { int64_t c = 0; for (auto& o : P.ops) c += o.invariant && !o.frozen; return c; }
   if (k == "n_kernels") return (int64_t)P.ops.size();
   if (k == "graph_builds") return P.graph_builds;
   if (k == "graph_launches") return P.graph_launches;
@@ -353,10 +391,7 @@ int64_t tq_plan_query(tq_plan p, const char* key) {
   if (k == "n_sweep_gates") return P.n_sweep_gates;
   if (k == "n_sweep2") { int64_t c = 0; for (auto& o : P.ops) c += o.kind == tq::OP_SWEEP2; return c; }
   if (k == "n_launch_once") {   // launches of the hoisted part as executed (chain launches merged)
-    int64_t c = P.n_launch_once;
-    if (P.use_seq) for (auto& r : P.seq_once) c -= r.second - r.first - 1;
-    if (P.use_coop) for (auto& r : P.coop_once) c -= r.second - r.first - 1;
-    return c;
+    return launches_in(P, P.use_seq, P.use_coop, P.n_sched_frozen, (int)P.sched_once.size());
   }
   if (k == "n_chain_launches") return P.use_seq ? (int64_t)P.seq_once.size() : 0;
   if (k == "n_coop_launches") return P.use_coop ? (int64_t)P.coop_once.size() : 0;
@@ -406,11 +441,10 @@ int64_t tq_plan_query(tq_plan p, const char* key) {
     if (k == "whole_flops") return (int64_t)W.flops;
     if (k == "whole_arena_bytes") return (int64_t)W.arena_bytes;
     if (k == "whole_resident_arena_bytes") return W.d_arena ? (int64_t)W.arena_bytes : 0;
-    if (k == "whole_n_launch") {   // launches as executed (chain launches merged)
-      int64_t c = W.n_launch_once + W.n_launch_slice;
-      if (P.use_seq) for (auto& r : W.seq_once) c -= r.second - r.first - 1;
-      return c;
+    if (k == "whole_n_launch") {   // launches as executed (chain launches merged), the frozen ones included
+      return launches_in(W, P.use_seq, false, 0, (int)W.sched_once.size()) - W.n_full_merged + W.n_launch_slice;
     }
+    if (const int64_t v = frozen_query(W, P.use_seq, false, k.substr(6)); v != -2) return v;
     if (k == "whole_n_s2_block_gate_work") return tq::plan_s2_gate_work(W, false);
     if (k == "whole_n_s2_prog_gate_work") return tq::plan_s2_gate_work(W, true);
   }

@@ -6,7 +6,9 @@
 //   * walks the SSA pairwise path, tracks which modes are still needed (mode reference counts),
 //     classifies every mode of each pair (batch / contracted / free / single-side sum),
 //   * marks the steps that read no sliced input (hoisted: run once per execute call, results
-//     pinned) and the two independent subtrees of the join step (branches, own arena regions),
+//     pinned), among them those that read no volatile input either (frozen: run once per binding,
+//     Plan::n_sched_frozen), and the two independent subtrees of the join step (branches, own
+//     arena regions),
 //   * picks per step the cheapest lowering:
 //       APPLY  one operand small (<= 32 x 32) and its contracted modes forming at most two runs
 //              in the big operand -> one streaming pass, no transpose (tq_apply.hip); the small
@@ -63,6 +65,7 @@ struct Live {
   BufRef buf;
   bool owned = false;  // arena intermediate that must be freed after use
   bool dep = false;    // depends on a sliced input (otherwise computed once per execute)
+  bool vol = true;     // depends on a sliced or a volatile input (otherwise frozen: Plan::frozen_valid)
   int64_t numel() const { return prod(ext); }
   bool contiguous() const {
     auto cs = contig_strides(ext);
@@ -159,8 +162,11 @@ class Compiler {
   // group_hint > 1: the plan will run in lockstep groups of that many plans (blocks as lanes,
   // plan_run_group), so every sweep op shares its launches with group_hint - 1 others
   // min_chunks > 0: the smallest chunk count of a big sweep op (else TQ_S2_MINCHUNKS / 128)
-  Compiler(Plan& P, int lanes_hint = 1, int group_hint = 1, int min_chunks = 0)
-      : P_(P), lanes_hint_(lanes_hint), group_hint_(std::max(1, group_hint)), min_chunks_(min_chunks) {}
+  // steady: per input, 1 = its contents stay the same between execute calls (not volatile);
+  // empty: every input is volatile
+  Compiler(Plan& P, int lanes_hint = 1, int group_hint = 1, int min_chunks = 0, std::vector<char> steady = {})
+      : P_(P), lanes_hint_(lanes_hint), group_hint_(std::max(1, group_hint)), min_chunks_(min_chunks),
+        steady_(std::move(steady)) {}
 
   int run(int n_inputs, const int32_t* in_ranks, const int32_t* in_modes, const int64_t* in_ext,
           const int64_t* in_strides, int out_rank, const int32_t* out_modes, int n_steps,
@@ -203,6 +209,7 @@ class Compiler {
       L.modes = v.modes; L.ext = v.ext; L.stride = v.stride;
       L.buf.kind = BUF_INPUT; L.buf.index = i; L.buf.off = 0;
       for (int64_t ss : v.slice_stride) L.dep |= ss != 0;
+      L.vol = L.dep || !(i < (int)steady_.size() && steady_[i]);
       P_.inputs.push_back(v);
       live_.push_back(L);
     }
@@ -228,19 +235,25 @@ class Compiler {
     // ---- pre-pass: which SSA ids depend on a sliced input, and which slice-invariant results
     // are read by slice-dependent steps (those are "pinned": kept in a region of their own that
     // no slice-dependent buffer ever reuses, since invariant ops do not re-run per slice)
+    // The same one tier down: a frozen result (no sliced and no volatile input in its subtree;
+    // the final step is never frozen) that a step of a later tier reads is pinned too, since a
+    // live-only execute call does not run the frozen ops again.  Tiers: 0 frozen, 1 hoisted, 2 per slice
     {
-      std::vector<char> dep(n_inputs + n_steps, 0);
-      for (int i = 0; i < n_inputs; ++i) dep[i] = live_[i].dep;
+      std::vector<char> tier(n_inputs + n_steps, 0);
+      for (int i = 0; i < n_inputs; ++i) tier[i] = live_[i].dep ? 2 : live_[i].vol ? 1 : 0;
       pinned_.assign(n_inputs + n_steps, 0);
+      std::set<int> fin;
       for (int s = 0; s < n_steps; ++s) {
         const int x = path[2 * s], y = path[2 * s + 1];
         if (x < 0 || y < 0 || x >= n_inputs + s || y >= n_inputs + s) break;  // checked below
-        dep[n_inputs + s] = dep[x] || dep[y];
-        if (dep[n_inputs + s]) {
-          if (!dep[x] && x >= n_inputs) pinned_[x] = 1;
-          if (!dep[y] && y >= n_inputs) pinned_[y] = 1;
-        }
+        const int t = std::max<int>({tier[x], tier[y], s == n_steps - 1 ? 1 : 0});
+        tier[n_inputs + s] = (char)t;
+        if (tier[x] < t && x >= n_inputs) pinned_[x] = 1;
+        if (tier[y] < t && y >= n_inputs) pinned_[y] = 1;
+        if (t == 0)
+          for (int z : {x, y}) if (z < n_inputs) fin.insert(z);
       }
+      P_.frozen_inputs.assign(fin.begin(), fin.end());
     }
     // ---- branches: the two subtrees of the join step are independent (run concurrently, arena
     // regions of their own); the join and every step outside its subtrees are branch 2 (region
@@ -396,8 +409,9 @@ class Compiler {
     if (P_.n_ps) tb += ((size_t)P_.n_slices * sizeof(uint32_t) + kAlign - 1) / kAlign * kAlign;
     P_.table_bytes = tb;
     for (auto& op : P_.ops) {
-      (op.invariant ? P_.flops_once : P_.flops_slice) += op.flops;
-      (op.invariant ? P_.bytes_once : P_.bytes_slice) += op.bytes;
+      (op.frozen ? P_.flops_frozen : op.invariant ? P_.flops_once : P_.flops_slice) += op.flops;
+      (op.frozen ? P_.bytes_frozen : op.invariant ? P_.bytes_once : P_.bytes_slice) += op.bytes;
+      if (op.frozen && op.c.kind == BUF_PINNED) P_.frozen_kept_bytes += (size_t)op.nc * P_.esz;
       P_.n_gemm += op.kind == OP_GEMM;
       P_.n_apply += op.kind == OP_APPLY;
       P_.n_permute += op.kind == OP_PERMUTE;
@@ -409,19 +423,25 @@ class Compiler {
     // (zero from the upload; every launch leaves its counter at zero)
     P_.sync_off = P_.table_bytes;
     P_.table_bytes += P_.coop_once.size() * Plan::kSyncSlot;
-    P_.flops = P_.flops_once + P_.flops_slice * (double)P_.n_slices;
-    P_.bytes = P_.bytes_once + P_.bytes_slice * (double)P_.n_slices;
+    P_.flops = P_.flops_frozen + P_.flops_once + P_.flops_slice * (double)P_.n_slices;
+    P_.bytes = P_.bytes_frozen + P_.bytes_once + P_.bytes_slice * (double)P_.n_slices;
     std::ostringstream d;
     for (size_t i = 0; i < P_.ops.size(); ++i)
-      d << (P_.ops[i].invariant ? "[once]  " : "[slice] ") << "b" << P_.ops[i].branch << " "
+      d << (P_.ops[i].frozen ? "[frozen] " : P_.ops[i].invariant ? "[once]  " : "[slice] ") << "b"
+        << P_.ops[i].branch << " "
         << P_.ops[i].note << "\n";
     d << "# schedule (launch: op indices)\n";
-    for (int set = 0; set < 2; ++set)
+    for (int set = 0; set < 2; ++set) {
+      int e = 0;
       for (auto& g : set == 0 ? P_.sched_once : P_.sched_slice) {
-        d << "# " << (set == 0 ? "once " : "slice");
+        d << "# " << (set == 1 ? "slice" : e++ < P_.n_sched_frozen ? "frozen" : "once ");
         for (int j : g) d << " " << j;
         d << "\n";
       }
+    }
+    for (auto& st : P_.full_steps)
+      if (st.first >= 0 && st.second >= 0)
+        d << "# full run: frozen entry " << st.first << " and once entry " << st.second << " share a launch\n";
     for (auto& r : P_.seq_once) {
       d << "# chain launch (a workgroup per stream, one-chunk layouts): once entries " << r.first << ".."
         << r.second - 1 << ", ops";
@@ -449,7 +469,7 @@ class Compiler {
   // C4 slice) for their max.  Words of slice-invariant producers are zeroed once per execute
   // call, the others before every slice.
   void assign_amax() {
-    P_.n_amax_once = P_.n_amax_slice = 0;
+    P_.n_amax_once = P_.n_amax_slice = P_.n_amax_frozen = 0;
     if (P_.dtype != TQ_C64) return;
     const int64_t esz = (int64_t)P_.esz;
     auto span = [&](const BufRef& b, int64_t n, int* space, int64_t* lo, int64_t* hi) {
@@ -460,7 +480,10 @@ class Compiler {
       *hi = *lo + n * esz;
       return true;
     };
-    std::vector<int> once, slice;  // producer op indices, in word order
+    std::vector<int> frozen, once, slice;  // producer op indices, in word order
+    auto words_of = [&](int j) -> std::vector<int>& {
+      return P_.ops[j].frozen ? frozen : P_.ops[j].invariant ? once : slice;
+    };
     auto producer = [&](int gi, const BufRef& r, int64_t n) -> int {
       int sp, spw;
       int64_t lo, hi, wlo, whi;
@@ -487,7 +510,7 @@ class Compiler {
       prod_a[i] = pa;
       prod_b[i] = pb;
       for (int j : {pa, pb}) {
-        auto& v = P_.ops[j].invariant ? once : slice;
+        auto& v = words_of(j);
         if (std::find(v.begin(), v.end(), j) == v.end()) v.push_back(j);
       }
     }
@@ -544,7 +567,7 @@ class Compiler {
         for (int r = 0; r < 2; ++r) {
           const int j = pab[r], x = planes_x[j];
           P_.ops[j].planes_role = r + 1;
-          auto& v = P_.ops[x].invariant ? once : slice;
+          auto& v = words_of(x);
           if (std::find(v.begin(), v.end(), x) == v.end()) v.push_back(x);
           // the planes (12 B per element) replace the complex64 store (8 B)
           P_.ops[j].bytes += (double)P_.ops[j].nc * 4.0;
@@ -555,9 +578,12 @@ class Compiler {
         P_.ops[P_.planes_gemm].note += " planes";
       }
     }
-    P_.n_amax_once = (int)once.size();
+    // words: [frozen producers][the other hoisted producers][per slice, a set per lane]
+    P_.n_amax_frozen = (int)frozen.size();
+    P_.n_amax_once = (int)(frozen.size() + once.size());
     P_.n_amax_slice = (int)slice.size();
-    for (size_t q = 0; q < once.size(); ++q) P_.ops[once[q]].amax_word = (int)q;
+    for (size_t q = 0; q < frozen.size(); ++q) P_.ops[frozen[q]].amax_word = (int)q;
+    for (size_t q = 0; q < once.size(); ++q) P_.ops[once[q]].amax_word = P_.n_amax_frozen + (int)q;
     for (size_t q = 0; q < slice.size(); ++q) P_.ops[slice[q]].amax_word = P_.n_amax_once + (int)q;
     for (size_t j = 0; j < P_.ops.size(); ++j)
       if (P_.ops[j].planes_role) P_.ops[j].planes_in_amax = P_.ops[planes_x[j]].amax_word;
@@ -641,9 +667,13 @@ class Compiler {
           if (a.space == b.space && a.lo < b.hi && b.lo < a.hi) return true;
       return false;
     };
-    for (int set = 0; set < 2; ++set) {
+    // three sets, in execution order: frozen, hoisted, per slice (the first two in sched_once)
+    P_.sched_once.clear();
+    P_.sched_slice.clear();
+    for (int set = 0; set < 3; ++set) {
       std::vector<int> ids;
-      for (size_t i = 0; i < n; ++i) if (P_.ops[i].invariant == (set == 0)) ids.push_back((int)i);
+      for (size_t i = 0; i < n; ++i)
+        if ((P_.ops[i].frozen ? 0 : P_.ops[i].invariant ? 1 : 2) == set) ids.push_back((int)i);
       std::vector<int> lev(ids.size(), 0);
       int maxlev = -1;
       for (size_t b = 0; b < ids.size(); ++b) {
@@ -655,8 +685,7 @@ class Compiler {
         }
         maxlev = std::max(maxlev, lev[b]);
       }
-      auto& sched = set == 0 ? P_.sched_once : P_.sched_slice;
-      sched.clear();
+      auto& sched = set < 2 ? P_.sched_once : P_.sched_slice;
       for (int L = 0; L <= maxlev; ++L) {
         std::vector<int> grp;
         for (size_t b = 0; b < ids.size(); ++b) {
@@ -668,8 +697,10 @@ class Compiler {
         }
         if (!grp.empty()) sched.push_back(grp);
       }
+      if (set == 0) P_.n_sched_frozen = (int)P_.sched_once.size();
     }
-    P_.n_launch_once = (int)P_.sched_once.size();
+    P_.n_launch_frozen = P_.n_sched_frozen;
+    P_.n_launch_once = (int)P_.sched_once.size() - P_.n_sched_frozen;
     P_.n_launch_slice = (int)P_.sched_slice.size();
     // chain launches: consecutive hoisted levels that are each one small sweep2 op (C2's whole
     // contraction, the first levels of C3 / C4's hoisted chains: 1-4 workgroups per launch) run
@@ -696,7 +727,8 @@ class Compiler {
       if (!chainable(P_.sched_once[i])) { ++i; continue; }
       std::vector<int> in_run;   // ops of the run so far
       int nstreams = 0, nops = 0, e = i;
-      for (; e < ns && chainable(P_.sched_once[e]); ++e) {
+      const int seg_end = i < P_.n_sched_frozen ? P_.n_sched_frozen : ns;   // (a run stays in its schedule)
+      for (; e < seg_end && chainable(P_.sched_once[e]); ++e) {
         const auto& g = P_.sched_once[e];
         if (nops + (int)g.size() > kS2MaxOps) break;
         std::vector<int> st(g.size(), -1);
@@ -807,7 +839,8 @@ class Compiler {
       if (!coop_ok(i)) { ++i; continue; }
       std::vector<Acc> gates, writes;
       int e = i;
-      for (; e < ns && coop_ok(e) && e - i < kS2MaxOps; ++e) {
+      const int seg_end = i < P_.n_sched_frozen ? P_.n_sched_frozen : ns;
+      for (; e < seg_end && coop_ok(e) && e - i < kS2MaxOps; ++e) {
         const int j = P_.sched_once[e][0];
         std::vector<Acc> g;
         for (auto& sg : P_.ops[j].sgates) add(g, sg.g, sg.n);
@@ -827,6 +860,59 @@ class Compiler {
         for (int q = i; q < e; ++q) P_.ops[P_.sched_once[q][0]].lds_io = s2_seq_prefetch() ? 4 : 0;
       }
       i = std::max(e, i + 1);
+    }
+    // The full run (a call that runs the frozen schedule too): the frozen entries and the hoisted
+    // ones in their own orders, zipped -- a hoisted plain sweep2 level that conflicts with no frozen
+    // entry still to come shares the launch of the next frozen plain sweep2 level, as the two
+    // halves' levels do in a plan that declares nothing.  Chain and cooperative runs stay whole
+    // and unmerged, and every op runs in the launch form it has in a live-only call (the same
+    // descriptor and chunks), so a full and a live-only call compute the same bits.
+    P_.full_steps.clear();
+    P_.n_full_merged = 0;
+    if (P_.n_sched_frozen > 0) {
+      const int nf = P_.n_sched_frozen;
+      // units of sched_once: a run (chain or cooperative) or one entry; [first, last)
+      auto units = [&](int b, int e) {
+        std::vector<std::pair<int, int>> u;
+        for (int i = b; i < e;) {
+          int last = i + 1;
+          for (auto& r : P_.seq_once) if (r.first == i) last = r.second;
+          for (auto& r : P_.coop_once) if (r.first == i) last = r.second;
+          u.push_back({i, last});
+          i = last;
+        }
+        return u;
+      };
+      const auto F = units(0, nf), L = units(nf, ns);
+      auto plain = [&](const std::pair<int, int>& u) {
+        if (u.second - u.first != 1) return false;
+        for (int j : P_.sched_once[u.first])
+          if (P_.ops[j].kind != OP_SWEEP2 || P_.ops[j].s2_dense) return false;
+        return true;
+      };
+      auto unit_conflict = [&](const std::pair<int, int>& a, const std::pair<int, int>& b) {
+        for (int x = a.first; x < a.second; ++x)
+          for (int y = b.first; y < b.second; ++y)
+            for (int i : P_.sched_once[x])
+              for (int j : P_.sched_once[y])
+                if (conflict(i, j)) return true;
+        return false;
+      };
+      size_t fi = 0, li = 0;
+      while (fi < F.size()) {
+        bool merge = li < L.size() && plain(F[fi]) && plain(L[li]) &&
+                     P_.sched_once[F[fi].first].size() + P_.sched_once[L[li].first].size() <= (size_t)kS2MaxOps;
+        for (size_t k = fi; merge && k < F.size(); ++k) merge = !unit_conflict(F[k], L[li]);
+        if (merge) {
+          P_.full_steps.push_back({F[fi].first, L[li].first});
+          ++P_.n_full_merged;
+          ++li;
+        } else {
+          P_.full_steps.push_back({F[fi].first, -1});
+        }
+        ++fi;
+      }
+      for (; li < L.size(); ++li) P_.full_steps.push_back({-1, L[li].first});
     }
   }
 
@@ -935,6 +1021,7 @@ class Compiler {
     }
     for (int m : B0.modes) if (!inA.count(m)) (cnt_[m] > 0 ? freeB : sumB).insert(m);
     const bool dep = A0.dep || B0.dep;
+    const bool vol = dep || A0.vol || B0.vol || final;   // (the final step is never frozen)
     const int nid = n_inputs_ + s;
 
     ApplyDesc d;
@@ -944,7 +1031,7 @@ class Compiler {
       const bool pendA = A0.buf.kind == BUF_PENDING, pendB = B0.buf.kind == BUF_PENDING;
       bool extended = false;
       if (can_apply && (d.a_big ? pendA : pendB) && !(d.a_big ? pendB : pendA) && dep == chain_.dep &&
-          br_ == chain_.br) {
+          vol == chain_.vol && br_ == chain_.br) {
         Chain::Gate g = make_gate(s, d, d.a_big ? B0 : A0, d.a_big ? A0 : B0, dep);
         chain_.gates.push_back(g);
         ChainShape sh;
@@ -968,6 +1055,7 @@ class Compiler {
         res.buf = BufRef{BUF_PENDING, nid, 0};
         res.owned = true;
         res.dep = dep;
+        res.vol = vol;
         for (int m : res.modes) cnt_[m]++;
         if (final) {
           live_.push_back(res);  // flush patches live_[id]; the caller's push is replaced below
@@ -985,6 +1073,7 @@ class Compiler {
       chain_ = Chain{};
       chain_.active = true;
       chain_.dep = dep;
+      chain_.vol = vol;
       chain_.br = br_;
       chain_.X0 = d.a_big ? A0 : B0;
       chain_.release_X0 = !(dep && !chain_.X0.dep);
@@ -999,6 +1088,7 @@ class Compiler {
         res.buf = BufRef{BUF_PENDING, nid, 0};
         res.owned = true;
         res.dep = dep;
+        res.vol = vol;
         for (int m : res.modes) cnt_[m]++;
         return TQ_OK;
       }
@@ -1013,8 +1103,10 @@ class Compiler {
     // slice-invariant hoisting: a step that reads no sliced input runs once per execute; its
     // result is pinned in the arena when a slice-dependent step consumes it
     res.dep = dep;
+    res.vol = vol;
     for (size_t k = first_op; k < P_.ops.size(); ++k) {
       P_.ops[k].invariant = !res.dep;
+      P_.ops[k].frozen = !vol;
       P_.ops[k].branch = br_;
     }
     if (!(res.dep && !A0.dep)) release(A0);
@@ -1146,6 +1238,7 @@ class Compiler {
     };
     bool active = false;
     bool dep = false;
+    bool vol = true;      // Live::vol of its steps (a chain does not cross a tier)
     int br = 0;           // branch of its steps
     int id = -1;          // SSA id of the (pending) chain result
     int flushed_id = -1;
@@ -2397,9 +2490,11 @@ class Compiler {
     }
     for (size_t k = first_op; k < P_.ops.size(); ++k) {
       P_.ops[k].invariant = !c.dep;
+      P_.ops[k].frozen = !c.vol;
       P_.ops[k].branch = c.br;
     }
     res.dep = c.dep;
+    res.vol = c.vol;
     // the pending result gets its real buffer
     Live& L = live_[c.id];
     L.buf = res.buf;
@@ -2408,6 +2503,7 @@ class Compiler {
     L.ext = res.ext;
     L.stride = res.stride;
     L.dep = c.dep;
+    L.vol = c.vol;
     // operands are released only now, after the result buffer was placed
     if (c.release_X0) release(c.X0);
     for (auto& g : c.gates) if (g.release) release(g.Sm);
@@ -2633,6 +2729,7 @@ class Compiler {
   int lanes_hint_ = 1;
   int group_hint_ = 1;
   int min_chunks_ = 0;
+  std::vector<char> steady_;
   bool one_chunk_ = false;   // s2_layout: one chunk of the whole tensor when it fits the tile
   bool cplx_ = false;
   int n_inputs_ = 0;
@@ -2653,7 +2750,8 @@ class Compiler {
 int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, const int32_t* in_modes,
                  const int64_t* in_extents, const int64_t* in_strides, int out_rank,
                  const int32_t* out_modes, int n_steps, const int32_t* path, int n_sliced,
-                 const int32_t* sliced_modes, int group_hint, int min_chunks) {
+                 const int32_t* sliced_modes, int group_hint, int min_chunks, int n_volatile,
+                 const int32_t* volatile_ids) {
   TQ_CHECK_ARG(dtype_valid(dtype), "dtype");
   TQ_CHECK_ARG(group_hint >= 1, "group_hint");
   TQ_CHECK_ARG(min_chunks >= 0, "min_chunks");
@@ -2661,9 +2759,19 @@ int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, cons
   TQ_CHECK_ARG(n_steps == n_inputs - 1, "a pairwise path has n_inputs - 1 steps");
   TQ_CHECK_ARG(out_rank >= 0 && out_rank <= TQ_MAX_RANK, "output rank");
   TQ_CHECK_ARG(n_sliced >= 0 && n_sliced <= 62, "n_sliced");
+  // declared volatile inputs: every other input is steady (n_volatile < 0: none is)
+  std::vector<char> steady;
+  if (n_volatile >= 0) {
+    TQ_CHECK_ARG(n_volatile == 0 || volatile_ids != nullptr, "null volatile input list");
+    steady.assign(n_inputs, 1);
+    for (int q = 0; q < n_volatile; ++q) {
+      TQ_CHECK_ARG(volatile_ids[q] >= 0 && volatile_ids[q] < n_inputs, "volatile input id out of range");
+      steady[volatile_ids[q]] = 0;
+    }
+  }
   P = Plan{};
   P.dtype = dtype;
-  Compiler c(P, 1, group_hint, min_chunks);
+  Compiler c(P, 1, group_hint, min_chunks, steady);
   TQ_TRY(c.run(n_inputs, in_ranks, in_modes, in_extents, in_strides, out_rank, out_modes, n_steps,
                path, n_sliced, sliced_modes));
   if (P.lanes > 1) {
@@ -2671,7 +2779,7 @@ int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, cons
     // a batch share their launches); kept if the second plan runs with the same lanes
     Plan Q{};
     Q.dtype = dtype;
-    Compiler c2(Q, P.lanes, group_hint, min_chunks);
+    Compiler c2(Q, P.lanes, group_hint, min_chunks, steady);
     if (c2.run(n_inputs, in_ranks, in_modes, in_extents, in_strides, out_rank, out_modes, n_steps,
                path, n_sliced, sliced_modes) == TQ_OK && Q.lanes == P.lanes)
       P = std::move(Q);
@@ -2689,6 +2797,9 @@ int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, cons
   a.out_modes.assign(out_modes, out_modes + out_rank);
   a.path.assign(path, path + 2 * n_steps);
   a.sliced.assign(sliced_modes, sliced_modes + n_sliced);
+  a.declared = n_volatile >= 0;
+  a.volatile_ids.clear();
+  if (n_volatile > 0) a.volatile_ids.assign(volatile_ids, volatile_ids + n_volatile);
   P.group_hint = group_hint;
   P.min_chunks = min_chunks;
   static const bool prog_default = env_on("TQ_S2_PROG");   // TQ_S2_PROG=0: every block pass on the interpreter
@@ -2701,7 +2812,7 @@ int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, cons
     // rounding, which the parity bounds pin)
     auto W = std::make_shared<Plan>();
     if (plan_compile(*W, dtype, n_inputs, in_ranks, in_modes, in_extents, in_strides, out_rank, out_modes,
-                     n_steps, path, 0, nullptr, group_hint, min_chunks) == TQ_OK) {
+                     n_steps, path, 0, nullptr, group_hint, min_chunks, n_volatile, volatile_ids) == TQ_OK) {
       bool slice_gemm = false;
       for (const Op& op : P.ops) slice_gemm = slice_gemm || (op.kind == OP_GEMM && !op.invariant);
       P.fold_ok = !slice_gemm && W->bytes <= P.bytes && W->flops <= P.flops && W->arena_bytes <= P.arena_bytes;
@@ -2781,18 +2892,49 @@ int64_t plan_s2_gate_work(const Plan& P, bool programs_only) {
   return (int64_t)w;
 }
 
+namespace {
+int recompile(Plan& P, const CompileArgs& a, int group_hint, int min_chunks);
+}
+
 int plan_recompile(Plan& P, int group_hint, int min_chunks) {
   TQ_CHECK_ARG(P.d_arena == nullptr && P.d_tables == nullptr, "a plan is recompiled before its first execute only");
   TQ_CHECK_ARG(!P.args.in_ranks.empty(), "plan has no compile arguments");
   if (group_hint == P.group_hint && min_chunks == P.min_chunks) return TQ_OK;
-  const CompileArgs a = P.args;
+  return recompile(P, P.args, group_hint, min_chunks);
+}
+
+int plan_set_volatile(Plan& P, int n, const int32_t* ids) {
+  TQ_CHECK_ARG(!P.resident && !(P.whole && P.whole->resident) && P.d_arena == nullptr && P.d_tables == nullptr,
+               "volatile inputs are declared before the plan's first execute only");
+  TQ_CHECK_ARG(!P.args.in_ranks.empty(), "plan has no compile arguments");
+  TQ_CHECK_ARG(n <= 0 || ids != nullptr, "null volatile input list");
+  CompileArgs a = P.args;
+  a.declared = n >= 0;
+  a.volatile_ids.clear();
+  if (n > 0) a.volatile_ids.assign(ids, ids + n);
+  std::sort(a.volatile_ids.begin(), a.volatile_ids.end());
+  a.volatile_ids.erase(std::unique(a.volatile_ids.begin(), a.volatile_ids.end()), a.volatile_ids.end());
+  if (a.declared == P.args.declared && a.volatile_ids == P.args.volatile_ids) return TQ_OK;
+  return recompile(P, a, P.group_hint, P.min_chunks);
+}
+
+void plan_frozen_invalidate(Plan& P) {
+  P.frozen_valid = false;
+  if (P.whole) P.whole->frozen_valid = false;
+}
+
+namespace {
+// compile P again from arguments `a0`, keeping its per-plan options
+int recompile(Plan& P, const CompileArgs& a0, int group_hint, int min_chunks) {
+  const CompileArgs a = a0;
   const bool seq = P.use_seq, coop = P.use_coop, planes = P.use_planes, graph = P.use_graph;
   const bool prog = P.use_s2_prog, fold = P.use_fold;
   Plan Q;
   TQ_TRY(plan_compile(Q, P.dtype, (int)a.in_ranks.size(), a.in_ranks.data(), a.in_modes.data(),
                       a.in_extents.data(), a.in_strides.empty() ? nullptr : a.in_strides.data(),
                       (int)a.out_modes.size(), a.out_modes.data(), (int)a.path.size() / 2, a.path.data(),
-                      (int)a.sliced.size(), a.sliced.data(), group_hint, min_chunks));
+                      (int)a.sliced.size(), a.sliced.data(), group_hint, min_chunks,
+                      a.declared ? (int)a.volatile_ids.size() : -1, a.volatile_ids.data()));
   Q.use_seq = seq;
   Q.use_coop = coop;
   Q.use_planes = planes;
@@ -2802,6 +2944,7 @@ int plan_recompile(Plan& P, int group_hint, int min_chunks) {
   P = std::move(Q);
   return TQ_OK;
 }
+}  // namespace
 
 void plan_clone_compiled(const Plan& src, Plan& dst) {
   dst = src;
@@ -2823,6 +2966,11 @@ void plan_clone_compiled(const Plan& src, Plan& dst) {
   dst.run_mode = 0;
   dst.resident = dst.fold_failed = false;
   dst.folded_executes = 0;
+  dst.frozen_valid = dst.live_only = false;
+  dst.frozen_ptrs.clear();
+  dst.frozen_ev = nullptr;
+  dst.frozen_stream = nullptr;
+  dst.frozen_runs = 0;
   if (src.whole) {
     dst.whole = std::make_shared<Plan>();
     plan_clone_compiled(*src.whole, *dst.whole);

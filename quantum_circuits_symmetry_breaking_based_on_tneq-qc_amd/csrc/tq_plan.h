@@ -40,6 +40,8 @@ struct Op {
   BufRef a, b, c;       // permute: a -> c ; gemm: c = a*b ; apply: c = a (x) b ; axpy: c += a
   bool writes_output = false;
   bool invariant = false;  // reads no sliced input: run once per execute call (hoisted)
+  bool frozen = false;     // hoisted, and reads no volatile input either (Plan::frozen_inputs only):
+                           // run when the plan's frozen results are not valid (Plan::frozen_valid)
   int branch = 0;          // 0 / 1: the two independent subtrees of the final step (own arena
                            // regions; their sweeps share launches); 2: the join (final step)
   // permute
@@ -120,6 +122,10 @@ struct InputView {
 struct CompileArgs {
   std::vector<int32_t> in_ranks, in_modes, out_modes, path, sliced;
   std::vector<int64_t> in_extents, in_strides;
+  // the inputs whose contents may change between two execute calls (plan_set_volatile); every
+  // input unless `declared`
+  bool declared = false;
+  std::vector<int32_t> volatile_ids;
 };
 
 struct Plan {
@@ -149,6 +155,9 @@ struct Plan {
   // n_amax_once + j * n_amax_slice)
   size_t amax_off = 0;
   int n_amax_once = 0, n_amax_slice = 0;
+  // the first n_amax_frozen of the n_amax_once words are written by frozen producers: zeroed with
+  // the others by a call that runs the frozen schedule, left alone by a live-only call
+  int n_amax_frozen = 0;
   // pre-split GEMMs: scale words (one per per-slice max word), one window flag per slice, and
   // the host copy of the flags (read after an execute call that ran pre-split GEMMs)
   size_t sc_off = 0, bad_off = 0;
@@ -186,13 +195,44 @@ struct Plan {
   struct Ev { hipEvent_t a, b; int kind; double flops, bytes; };
   std::vector<Ev> ev_used, ev_free;
   double flops = 0, bytes = 0;              // whole execute (all slices)
-  double flops_once = 0, bytes_once = 0;    // slice-invariant (hoisted) part
+  double flops_once = 0, bytes_once = 0;    // slice-invariant (hoisted) part without the frozen ops
+  double flops_frozen = 0, bytes_frozen = 0;  // frozen ops (a call that runs them pays these too)
   double flops_slice = 0, bytes_slice = 0;  // per slice
   int n_gemm = 0, n_apply = 0, n_permute = 0, n_sweep = 0, n_sweep_gates = 0;
   // launch schedule: ops grouped by dependency level; independent sweep2 ops of one level share
   // a launch.  `once` = slice-invariant ops (first slice of an execute call), `slice` = per slice
   std::vector<std::vector<int>> sched_once, sched_slice;
   int n_launch_once = 0, n_launch_slice = 0;
+  // Frozen results.  A plan may be told which inputs are volatile (CompileArgs::volatile_ids):
+  // a step whose subtree holds no volatile and no sliced input is frozen, and so is an op whose
+  // steps all are (never one that writes the output).  The frozen ops have a schedule of their own,
+  // built like the other two: the first n_sched_frozen entries of sched_once (n_launch_once counts
+  // the entries behind them; chain and cooperative runs never cross the boundary).  A frozen result
+  // that a later schedule reads is pinned (BUF_PINNED: no other buffer reuses its bytes), the other
+  // frozen intermediates share the ordinary regions, since the frozen schedule runs before the rest.
+  // Run time (tq_plan_run.cpp): the frozen schedule runs when the results are not valid -- first
+  // call, a frozen input's pointer differs from the one remembered, tq_plan_set "frozen_valid" 0,
+  // an execute call that failed -- and the call is not enqueued into a caller's capture (which
+  // always runs everything and leaves this state alone).  Every other call is live-only: it
+  // starts at entry n_sched_frozen, does not zero the frozen max words, and on another stream than
+  // the one the frozen schedule ran on first waits for frozen_ev.  A call that does run the frozen
+  // schedule follows full_steps (below).
+  int n_sched_frozen = 0, n_launch_frozen = 0;
+  // the full run (a call that runs the frozen schedule): units of sched_once in execution order,
+  // {frozen unit, hoisted unit} by their first entry (-1: none); a unit is a chain / cooperative
+  // run or one entry.  Both set: two plain sweep2 levels that share one launch (n_full_merged of
+  // them) -- a hoisted level that no frozen entry still to come conflicts with.  A live-only call
+  // runs the hoisted entries [n_sched_frozen, end) alone, each op in the same launch form
+  std::vector<std::pair<int, int>> full_steps;
+  int n_full_merged = 0;
+  std::vector<int> frozen_inputs;           // the inputs the frozen ops' subtrees read
+  size_t frozen_kept_bytes = 0;             // pinned results of frozen ops
+  bool frozen_valid = false;
+  bool live_only = false;                   // this execute call skips the frozen schedule
+  std::vector<const void*> frozen_ptrs;     // per frozen_inputs entry: the pointer computed from
+  hipEvent_t frozen_ev = nullptr;           // recorded behind the frozen schedule's last run
+  hipStream_t frozen_stream = nullptr;      // ... on this stream
+  int64_t frozen_runs = 0;                  // execute calls that ran the frozen schedule
   // chain launches: runs [first, last) of consecutive sched_once entries that are each ONE small
   // sweep2 op (a one-chunk layout exists), run in order by one workgroup in one launch
   // (S2Launch::seq) when use_seq (env TQ_S2_SEQ, default 1; tq_plan_set "sweep_chain")
@@ -237,11 +277,12 @@ struct Plan {
     bool seq = true;  // Plan::use_seq
     bool coop = false;  // Plan::use_coop
     int prog = 0;   // 1: the call ran the whole program (Plan::whole)
+    int live = 0;   // 1: the call skipped the frozen schedule (Plan::live_only)
     // a group execute (plan_run_group): every member's output and serial
     std::vector<const void*> group;
     bool operator==(const GraphKey& o) const {
       return inputs == o.inputs && out == o.out && b == o.b && e == o.e && s == o.s && acc == o.acc &&
-             mode == o.mode && seq == o.seq && coop == o.coop && planes == o.planes && prog == o.prog && group == o.group;
+             mode == o.mode && seq == o.seq && coop == o.coop && planes == o.planes && prog == o.prog && live == o.live && group == o.group;
     }
   };
   bool use_graph = true;
@@ -266,10 +307,17 @@ struct Plan {
 int plan_compile(Plan& P, int dtype, int n_inputs, const int32_t* in_ranks, const int32_t* in_modes,
                  const int64_t* in_extents, const int64_t* in_strides, int out_rank,
                  const int32_t* out_modes, int n_steps, const int32_t* path, int n_sliced,
-                 const int32_t* sliced_modes, int group_hint = 1, int min_chunks = 0);
+                 const int32_t* sliced_modes, int group_hint = 1, int min_chunks = 0,
+                 int n_volatile = -1, const int32_t* volatile_ids = nullptr);
 // compile the plan again for lockstep groups of `group_hint` plans and with `min_chunks` (0:
 // the default) chunks per big sweep op at least (before its first execute)
 int plan_recompile(Plan& P, int group_hint, int min_chunks);
+// compile the plan again with inputs `ids` declared volatile (n < 0: every input, the default):
+// what the other inputs' subtrees hold is computed once and kept (Plan::frozen_valid); before the
+// plan's first execute
+int plan_set_volatile(Plan& P, int n, const int32_t* ids);
+// forget the frozen results of the plan's programs: the next execute call computes them again
+void plan_frozen_invalidate(Plan& P);
 // write (on) or clear (off) the program ids of every plain register-block pass in the plan's
 // sweep2 descriptors (host copies: before the tables are uploaded)
 void plan_s2_programs(Plan& P, bool on);

@@ -6,7 +6,8 @@
 // the slice-lane mechanism with an instance index -- so G amplitude blocks in flight cost the
 // launches of one; the other ops (GEMM, permute, lane sum, ...) run per instance, member k > 0 on
 // a side stream of its own.  A group of one plan is exactly the single-plan executor.
-// Per execute call: the hoisted (slice-invariant) schedule once -- single launches, chain launches
+// Per execute call: the hoisted (slice-invariant) schedule once -- without its frozen entries when
+// the call is live-only (Plan::live_only) -- as single launches, chain launches
 // (Plan::seq_once) and opt-in cooperative chain launches (Plan::coop_once) -- then the per-slice
 // schedule for every batch of Plan::lanes slices: sweep2 levels merged across the batch's lanes,
 // lane-batched GEMMs, lane sums, and lane by lane whatever writes the output.
@@ -591,26 +592,55 @@ int Exec::run(int64_t s_begin, int64_t s_end, int64_t s_step, int accumulate) {
       // (all-zero / all-NaN outputs; mis-ordered node or carried-over max: DESIGN.md §5)
       // one launch for the hoisted part's words and (not pre-split) the first batch's per-slice
       // words behind them
+      // a live-only call (Plan::live_only: the frozen results are valid) leaves the frozen
+      // producers' words as they are and starts behind the frozen schedule
+      const bool live = P0_.live_only;
       for (auto& x : I_) {
         const int n = x.P->n_amax_once + (x.P->run_mode ? 0 : x.P->n_amax_slice * nl);
-        TQ_TRY(zero_words_launch(amax_word(x, 0), n, st_));
+        const int z0 = live ? x.P->n_amax_frozen : 0;
+        TQ_TRY(zero_words_launch(amax_word(x, z0), n - z0, st_));
       }
-      size_t run = 0, crun = 0;
-      for (int i = 0; i < (int)P0_.sched_once.size();) {
-        while (P0_.use_seq && run < P0_.seq_once.size() && P0_.seq_once[run].first < i) ++run;
-        if (P0_.use_seq && run < P0_.seq_once.size() && P0_.seq_once[run].first == i) {
-          TQ_TRY(launch_chain(i, P0_.seq_once[run].second, -1));
-          i = P0_.seq_once[run].second;
-          continue;
+      // entries [b, e) of sched_once: chain / cooperative runs as one launch each, the rest singly
+      auto entries = [&](int b, int e) -> int {
+        size_t run = 0, crun = 0;
+        for (int i = b; i < e;) {
+          while (P0_.use_seq && run < P0_.seq_once.size() && P0_.seq_once[run].first < i) ++run;
+          if (P0_.use_seq && run < P0_.seq_once.size() && P0_.seq_once[run].first == i) {
+            TQ_TRY(launch_chain(i, P0_.seq_once[run].second, -1));
+            i = P0_.seq_once[run].second;
+            continue;
+          }
+          while (P0_.use_coop && crun < P0_.coop_once.size() && P0_.coop_once[crun].first < i) ++crun;
+          if (P0_.use_coop && crun < P0_.coop_once.size() && P0_.coop_once[crun].first == i) {
+            TQ_TRY(launch_chain(i, P0_.coop_once[crun].second, (int)crun));
+            i = P0_.coop_once[crun].second;
+            continue;
+          }
+          TQ_TRY(launch(P0_.sched_once[i]));
+          ++i;
         }
-        while (P0_.use_coop && crun < P0_.coop_once.size() && P0_.coop_once[crun].first < i) ++crun;
-        if (P0_.use_coop && crun < P0_.coop_once.size() && P0_.coop_once[crun].first == i) {
-          TQ_TRY(launch_chain(i, P0_.coop_once[crun].second, (int)crun));
-          i = P0_.coop_once[crun].second;
-          continue;
+        return TQ_OK;
+      };
+      // the end of the unit (a run, or one entry) that starts at entry i
+      auto unit_end = [&](int i) {
+        for (auto& r : P0_.seq_once) if (r.first == i) return r.second;
+        for (auto& r : P0_.coop_once) if (r.first == i) return r.second;
+        return i + 1;
+      };
+      if (live || P0_.full_steps.empty()) {
+        TQ_TRY(entries(live ? P0_.n_sched_frozen : 0, (int)P0_.sched_once.size()));
+      } else {
+        // the full run of a plan with frozen ops (Plan::full_steps): both schedules, zipped
+        for (auto& st : P0_.full_steps) {
+          if (st.first >= 0 && st.second >= 0) {
+            std::vector<int> both = P0_.sched_once[st.first];
+            both.insert(both.end(), P0_.sched_once[st.second].begin(), P0_.sched_once[st.second].end());
+            TQ_TRY(launch(both));
+          } else {
+            const int i = st.first >= 0 ? st.first : st.second;
+            TQ_TRY(entries(i, unit_end(i)));
+          }
         }
-        TQ_TRY(launch(P0_.sched_once[i]));
-        ++i;
       }
     }
     // per-slice max words: one set per lane (pre-split mode: one set shared by the batch's

@@ -5,6 +5,8 @@
 //   * plan_prepare takes the device memory of the program an execute call runs -- the slice lanes,
 //     or the plan's whole program (Plan::whole) when the call covers every slice (plan_folds) --
 //     at that program's first use;
+//   * frozen_begin / frozen_ran keep a program's frozen results (Plan::n_sched_frozen): which
+//     pointers they were computed from, whether a call may skip their schedule, the event behind it;
 //   * plan_run checks the call, picks the pre-split mode, runs the call (plan_launch) and re-runs
 //     the slices whose pre-split scale window was missed; plan_run_group does the same for a
 //     lockstep group of plans compiled from one network;
@@ -226,17 +228,60 @@ int graph_run(Plan& P, const Plan::GraphKey& key, hipStream_t stream, Enqueue&& 
   return TQ_OK;
 }
 
+// Frozen results of program R (Plan::n_sched_frozen > 0), before an execute call with `inputs` on
+// `stream`: *live = the call skips the frozen schedule (the results are valid and were computed
+// from these pointers; on another stream than theirs the call first waits for them), *track = the
+// call updates the state afterwards (frozen_ran).  A call enqueued into a caller's capture runs
+// everything and leaves the state alone: a capture must not bake in the skip.
+int frozen_begin(Plan& R, const void* const* inputs, bool empty, hipStream_t stream, bool* live, bool* track) {
+  *live = *track = false;
+  R.live_only = false;
+  if (!R.n_sched_frozen || empty) return TQ_OK;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  TQ_HIP(hipStreamIsCapturing(stream, &cs));
+  if (cs != hipStreamCaptureStatusNone) return TQ_OK;
+  *track = true;
+  bool ok = R.frozen_valid && R.frozen_ptrs.size() == R.frozen_inputs.size();
+  for (size_t q = 0; ok && q < R.frozen_inputs.size(); ++q) ok = inputs[R.frozen_inputs[q]] == R.frozen_ptrs[q];
+  if (!ok) {
+    R.frozen_valid = false;
+    return TQ_OK;
+  }
+  if (stream != R.frozen_stream) TQ_HIP(hipStreamWaitEvent(stream, R.frozen_ev, 0));
+  *live = R.live_only = true;
+  return TQ_OK;
+}
+
+// ... after a tracked call that ran the frozen schedule: remember the pointers, record the event
+int frozen_ran(Plan& R, const void* const* inputs, hipStream_t stream) {
+  R.frozen_ptrs.clear();
+  for (int i : R.frozen_inputs) R.frozen_ptrs.push_back(inputs[i]);
+  if (!R.frozen_ev) TQ_HIP(hipEventCreateWithFlags(&R.frozen_ev, hipEventDisableTiming));
+  TQ_HIP(hipEventRecord(R.frozen_ev, stream));
+  R.frozen_stream = stream;
+  R.frozen_valid = true;
+  ++R.frozen_runs;
+  return TQ_OK;
+}
+
 // one execute call of one plan: eagerly, or as the replay of its hipGraph.  W: the plan's whole
 // program when the call runs it (its one "slice" is the sum over every slice); the graph is P's
 int plan_launch(Plan& P, Plan* W, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
                 int64_t s_step, int accumulate, hipStream_t stream) {
+  Plan& R = W ? *W : P;
+  bool live = false, track = false;
+  TQ_TRY(frozen_begin(R, inputs, !W && s_begin >= s_end, stream, &live, &track));
   auto enqueue = [&](hipStream_t s) {
     if (W) return plan_enqueue(*W, inputs, out, 0, 1, 1, accumulate, s);
     return plan_enqueue(P, inputs, out, s_begin, s_end, s_step, accumulate, s);
   };
+  auto done = [&](int rc) {
+    if (rc == TQ_OK && track && !live) rc = frozen_ran(R, inputs, stream);
+    return rc;
+  };
   bool eager = true;
   TQ_TRY(run_eagerly(P, stream, &eager));
-  if (eager) return enqueue(stream);
+  if (eager) return done(enqueue(stream));
   Plan::GraphKey key;
   key.inputs.assign(inputs, inputs + P.n_inputs);
   key.out = out; key.b = s_begin; key.e = s_end; key.s = s_step; key.acc = accumulate;
@@ -245,20 +290,23 @@ int plan_launch(Plan& P, Plan* W, const void* const* inputs, void* out, int64_t 
   key.seq = P.use_seq;
   key.coop = P.use_coop;
   key.prog = W ? 1 : 0;
-  return graph_run(P, key, stream, enqueue);
+  key.live = live ? 1 : 0;
+  return done(graph_run(P, key, stream, enqueue));
 }
 
 // the plans of a group are the same compiled network (identical op lists and schedules)
 bool same_structure(const Plan& a, const Plan& b) {
   if (a.dtype != b.dtype || a.ops.size() != b.ops.size() || a.sched_once != b.sched_once ||
-      a.sched_slice != b.sched_slice || a.lanes != b.lanes || a.n_slices != b.n_slices ||
-      a.seq_once != b.seq_once || a.seq_stream != b.seq_stream || a.use_seq != b.use_seq ||
-      a.use_coop != b.use_coop || a.coop_once != b.coop_once || a.n_inputs != b.n_inputs ||
+      a.sched_slice != b.sched_slice || a.n_sched_frozen != b.n_sched_frozen || a.full_steps != b.full_steps ||
+      a.lanes != b.lanes ||
+      a.n_slices != b.n_slices || a.seq_once != b.seq_once || a.seq_stream != b.seq_stream ||
+      a.use_seq != b.use_seq || a.use_coop != b.use_coop || a.coop_once != b.coop_once || a.n_inputs != b.n_inputs ||
       planes_active(a) != planes_active(b) || a.planes_gemm != b.planes_gemm)
     return false;
   for (size_t i = 0; i < a.ops.size(); ++i)
     if (a.ops[i].kind != b.ops[i].kind || a.ops[i].stab != b.ops[i].stab || a.ops[i].stab1 != b.ops[i].stab1 ||
-        a.ops[i].invariant != b.ops[i].invariant || a.ops[i].writes_output != b.ops[i].writes_output)
+        a.ops[i].invariant != b.ops[i].invariant || a.ops[i].frozen != b.ops[i].frozen ||
+        a.ops[i].writes_output != b.ops[i].writes_output)
       return false;
   return true;
 }
@@ -299,12 +347,42 @@ int plan_release(Plan& P) {
   }
   if (P.h_bad && rel(hipHostFree(P.h_bad), "host flag", rc)) P.h_bad = nullptr;
   if (P.d_planes && rel(hipFree(P.d_planes), "planes", rc)) P.d_planes = nullptr;
+  // (the frozen results go with the arena)
+  P.frozen_valid = false;
+  if (P.frozen_ev && rel(hipEventDestroy(P.frozen_ev), "frozen event", rc)) P.frozen_ev = nullptr;
   if (!P.d_arena && !P.d_tables) P.resident = false;
   return rc;
 }
 
+namespace {
+int run_one(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
+            int64_t s_step, int accumulate, hipStream_t stream);
+int run_group(Plan* const* plans, int n, const void* const* const* inputs, void* const* outs, int64_t s_begin,
+              int64_t s_end, int64_t s_step, int accumulate, hipStream_t stream);
+}  // namespace
+
+// (an execute call that returned an error leaves no frozen results behind)
 int plan_run(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
              int64_t s_step, int accumulate, hipStream_t stream) {
+  const int rc = run_one(P, inputs, out, s_begin, s_end, s_step, accumulate, stream);
+  if (rc != TQ_OK) plan_frozen_invalidate(P);
+  return rc;
+}
+
+int plan_run_group(Plan* const* plans, int n, const void* const* const* inputs, void* const* outs, int64_t s_begin,
+                   int64_t s_end, int64_t s_step, int accumulate, hipStream_t stream) {
+  TQ_CHECK_ARG(n >= 1 && plans && inputs && outs, "empty group");
+  if (n == 1) return plan_run(*plans[0], inputs[0], outs[0], s_begin, s_end, s_step, accumulate, stream);
+  const int rc = run_group(plans, n, inputs, outs, s_begin, s_end, s_step, accumulate, stream);
+  if (rc != TQ_OK)
+    for (int k = 0; k < n; ++k) plan_frozen_invalidate(*plans[k]);
+  return rc;
+}
+
+namespace {
+
+int run_one(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int64_t s_end,
+            int64_t s_step, int accumulate, hipStream_t stream) {
   TQ_CHECK_ARG(s_step >= 1, "slice_step");
   TQ_CHECK_ARG(s_begin >= 0 && s_end <= P.n_slices, "slice range");
   // the whole program runs a call over every slice once its memory is there (plan_prepare)
@@ -386,16 +464,15 @@ int plan_run(Plan& P, const void* const* inputs, void* out, int64_t s_begin, int
         if (batched ? P.h_bad[batch[0]] != 0 : P.h_bad[q] != 0) redo.push_back(q);
     }
     P.run_mode = 0;
+    P.live_only = P.n_sched_frozen > 0 && P.frozen_valid;   // (the call above has left them valid)
     for (int64_t sl : redo) TQ_TRY(plan_enqueue(P, inputs, out, sl, sl + 1, 1, 1, stream));
     P.ps_fallbacks += (int64_t)redo.size();
   }
   return TQ_OK;
 }
 
-int plan_run_group(Plan* const* plans, int n, const void* const* const* inputs, void* const* outs, int64_t s_begin,
-                   int64_t s_end, int64_t s_step, int accumulate, hipStream_t stream) {
-  TQ_CHECK_ARG(n >= 1 && plans && inputs && outs, "empty group");
-  if (n == 1) return plan_run(*plans[0], inputs[0], outs[0], s_begin, s_end, s_step, accumulate, stream);
+int run_group(Plan* const* plans, int n, const void* const* const* inputs, void* const* outs, int64_t s_begin,
+              int64_t s_end, int64_t s_step, int accumulate, hipStream_t stream) {
   Plan& P0 = *plans[0];
   TQ_CHECK_ARG(s_step >= 1, "slice_step");
   TQ_CHECK_ARG(s_begin >= 0 && s_end <= P0.n_slices, "slice range");
@@ -431,9 +508,23 @@ int plan_run_group(Plan* const* plans, int n, const void* const* const* inputs, 
   };
   if (fold)
     for (int k = 0; k < n; ++k) ++plans[k]->folded_executes;
+  // the group is live-only when every member's frozen results are valid; otherwise every member
+  // runs its frozen schedule again (idempotent; one rule keeps the lockstep schedule uniform)
+  bool live = true, track = true;
+  for (int k = 0; k < n; ++k) {
+    bool lk = false, tk = false;
+    TQ_TRY(frozen_begin(*run[k], inputs[k], !fold && s_begin >= s_end, stream, &lk, &tk));
+    live = live && lk;
+    track = track && tk;
+  }
+  for (int k = 0; k < n; ++k) run[k]->live_only = live;
+  auto done = [&](int rc) {
+    for (int k = 0; k < n && rc == TQ_OK && track && !live; ++k) rc = frozen_ran(*run[k], inputs[k], stream);
+    return rc;
+  };
   bool eager = true;
   TQ_TRY(run_eagerly(P0, stream, &eager));
-  if (eager) return enqueue(stream);
+  if (eager) return done(enqueue(stream));
   // one hipGraph of the whole group, cached in the first plan under every member's serial,
   // inputs and output (a serial is never reused, so a replay cannot address a freed plan)
   Plan::GraphKey key;
@@ -446,7 +537,10 @@ int plan_run_group(Plan* const* plans, int n, const void* const* const* inputs, 
   key.planes = planes_active(*run[0]) ? 1 : 0;
   key.seq = P0.use_seq;
   key.prog = fold ? 1 : 0;
-  return graph_run(P0, key, stream, enqueue);
+  key.live = live ? 1 : 0;
+  return done(graph_run(P0, key, stream, enqueue));
 }
+
+}  // namespace
 
 }  // namespace tq

@@ -78,6 +78,17 @@ class NativePlan:
         more, default 1 = TQ_FOLD_SLICES; before the first execute)."""
         check(_lib.lib().tq_plan_set(self._h, key.encode(), int(value)), "tq_plan_set")
 
+    def set_volatile(self, input_ids: Optional[Sequence[int]]) -> None:
+        """Declare the inputs whose contents may change between two execute calls
+        (tq_plan_set_volatile; None: every input, the default); before the first execute.  What
+        the other inputs' subtrees hold is then computed by the first call only and kept."""
+        if input_ids is None:
+            rc = _lib.lib().tq_plan_set_volatile(self._h, -1, None)
+        else:
+            ids = [int(i) for i in input_ids]
+            rc = _lib.lib().tq_plan_set_volatile(self._h, len(ids), i32(ids))
+        check(rc, "tq_plan_set_volatile")
+
     def describe(self) -> str:
         L = _lib.lib()
         n = L.tq_plan_describe(self._h, None, 0)
@@ -236,13 +247,17 @@ class HipContractExpression:
         return p
 
     # -- execution ---------------------------------------------------------------------------
-    def bind(self, *tensors, private_plan: bool = False) -> "BoundOperands":
+    def bind(self, *tensors, private_plan: bool = False, volatile: Optional[Sequence[int]] = None) -> "BoundOperands":
         """Validate `tensors` once (shapes, device, dtype, strides) and return the plan bound to
         their storage.  The binding reads whatever values those tensors hold when it runs, so an
         owner that updates operand VALUES in place (a sampler's projector vectors) runs it again
         without re-validation; the tensors themselves must stay alive and keep their storage,
         shapes and strides (the binding holds references to them).  `private_plan`: a clone of
-        the expression's plan owned by this binding (one per stream / block in flight)."""
+        the expression's plan owned by this binding (one per stream / block in flight).
+        `volatile` (private plans only): the operands whose values the owner changes between
+        runs (NativePlan.set_volatile); it must not write the others without `invalidate()`."""
+        if volatile is not None and not private_plan:
+            raise ValueError("bind(volatile=...) needs private_plan=True (the shared plan serves other callers)")
         if len(tensors) != len(self.net.terms):
             raise ValueError(f"expression takes {len(self.net.terms)} operands, got {len(tensors)}")
         ts = list(tensors)
@@ -263,6 +278,8 @@ class HipContractExpression:
         plan = self.plan(dt, None if contiguous else [t.stride() for t in ts], dev.index)
         if private_plan:
             plan = plan.clone()
+            if volatile is not None:
+                plan.set_volatile(volatile)
         return BoundOperands(self, plan, plan.pointer_array([t.data_ptr() for t in ts]), tuple(ts), dev, dt)
 
     def __call__(self, *tensors, out: Optional[torch.Tensor] = None, slice_range=None,
@@ -445,6 +462,11 @@ class BoundOperands:
 
     def new_out(self) -> torch.Tensor:
         return torch.empty(self.expr.out_shape, dtype=self.dtype, device=self.device)
+
+    def invalidate(self) -> None:
+        """Forget what the plan keeps of its non-volatile operands (bind(volatile=...)): call it
+        after writing into one of them in place; the next run computes those results again."""
+        self.plan.set("frozen_valid", 0)
 
     def _check_out(self, out: torch.Tensor) -> None:
         if (tuple(out.shape) != self.expr.out_shape or out.dtype != self.dtype or not out.is_contiguous()

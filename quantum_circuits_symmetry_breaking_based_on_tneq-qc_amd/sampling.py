@@ -18,6 +18,11 @@ its last member is enqueued (or by `flush()`).  Block b's projector vectors come
 table built once (`blocks` given up front); a group launch first copies its members' rows into
 the members' projector buffers on the slot's stream (one copy when the rows are consecutive).
 
+Between two blocks only the projectors that differ somewhere in the block table change: the
+pipeline declares exactly those volatile (`NativePlan.set_volatile`), so every member's plan
+contracts the subtrees that hold none of them -- for consecutive `with_batch` indices below 2^17
+on C4 the whole right half, its GEMM-operand producer included -- in its first launch only.
+
 Operand contract: the pipeline OWNS its operands and binds every member's plan to them once
 (`HipContractExpression.bind`, private plans): the projector buffers are updated IN PLACE between
 launches (ordinary stream-ordered copies) and the bound plans read the new values at run time --
@@ -64,7 +69,7 @@ class BlockPipeline:
 
     def __init__(self, task: AmplitudeTask, blocks: Sequence[int], inflight: int = 2, group: int = 1,
                  device: Optional[torch.device] = None, dtype: torch.dtype = torch.complex64,
-                 min_chunks: Optional[int] = None):
+                 min_chunks: Optional[int] = None, freeze: bool = True):
         if inflight < 1 or group < 1:
             raise ValueError("inflight and group must be >= 1")
         if len(blocks) == 0:
@@ -97,6 +102,13 @@ class BlockPipeline:
         if self.group > 1:
             # compiled for lockstep groups: wider sweep chunks (G ops share every launch)
             plan.set("group_hint", self.group)
+        # volatile operands: exactly the projectors whose rows differ anywhere in the block table
+        # (the pipeline owns every other operand and never writes them), so what the rest of the
+        # network contracts to is computed by each member's first launch only
+        # (`freeze=False`: nothing is declared, every launch contracts the whole network)
+        self.volatile = ([i for j, i in enumerate(self.proj) if bool((tab[:, j] != tab[0, j]).any())]
+                         if freeze else None)
+        plan.set_volatile(self.volatile)
         self.slots: List[_Slot] = []
         for s in range(self.inflight):
             stream = torch.cuda.current_stream(self.device) if s == 0 else torch.cuda.Stream(self.device)
@@ -106,7 +118,7 @@ class BlockPipeline:
                 ops = list(base_ops)
                 for j, i in enumerate(self.proj):
                     ops[i] = pbuf[m, j]
-                bound.append(self.expr.bind(*ops, private_plan=True))
+                bound.append(self.expr.bind(*ops, private_plan=True, volatile=self.volatile))
                 outs.append(torch.empty(self.expr.out_shape, dtype=dtype, device=self.device))
             self.slots.append(_Slot(stream, pbuf, bound, outs))
         self.k = 0
