@@ -294,6 +294,33 @@ int tq_born_sample(int dtype, int64_t n, const void* amps, int64_t n_draws, cons
                    int64_t* index, double* prob, double* stats, int n_axes, const int32_t* axis_qubit,
                    uint64_t base, void* workspace, size_t ws_bytes, void* stream);
 
+/* The k most probable elements of a block of n complex amplitudes (dtype TQ_C64 / TQ_C128,
+ * contiguous, device): post-selection, the other consumer of tq_plan_execute's output.  The
+ * reference has no counterpart; the nearest thing is EngineSiamese.sample.
+ *   p_i = re(a_i)^2 + im(a_i)^2 in float64 (complex64 widened first; both products and the sum
+ *   rounded on their own, no FP contraction: numpy's p bit for bit).
+ *   The candidates are the elements with p_i > 0: +inf counts, NaN and 0 never do.  They are
+ *   ordered by p descending and by index ascending among equal p.  With m = min(k, #candidates):
+ *   index[j] = the j-th candidate and prob[j] = its p (the float64 the order was decided on) for
+ *   j < m; index[j] = -1 and prob[j] = 0 for m <= j < k; count[0] = m.
+ * index: k int64, prob: k float64, count: one int64 (all device, 8-byte aligned, none NULL).
+ * 1 <= n <= 2^31, 1 <= k <= TQ_BORN_TOPK_MAX_K; k may exceed n.  The result is exact (no
+ * tolerance) and the same inputs give the same bits: the select counts with integer atomics and
+ * the final order is a total one.
+ * axis_qubit, n_axes, base: exactly as in tq_born_sample (index[j] becomes the bitstring word;
+ * n == 2^n_axes, entries distinct and in [0, 62], base clear at the axis qubits; -1 stays -1).
+ * workspace: tq_born_topk_workspace(dtype, n, k) bytes of device memory, 8-byte aligned (the
+ * query is host-only: 0 and a tq_last_error message for bad arguments); it need not be zeroed,
+ * the call's own kernels zero what they count in.  Every argument is checked before anything is
+ * launched; the call allocates, copies and synchronises nothing, and its launch sequence depends
+ * only on (dtype, n, k), never on the data, so it may be captured into a graph and replayed on
+ * other data.                                                                                 */
+#define TQ_BORN_TOPK_MAX_K 4096
+size_t tq_born_topk_workspace(int dtype, int64_t n, int64_t k);
+int tq_born_topk(int dtype, int64_t n, const void* amps, int64_t k, int64_t* index, double* prob,
+                 int64_t* count, int n_axes, const int32_t* axis_qubit, uint64_t base,
+                 void* workspace, size_t ws_bytes, void* stream);
+
 /* Fidelity loss of the symmetry-breaking fit (symmetry_breaking_quantum.py:220-229, the loss of
  * every pruning candidate; validate_target_tensor :159-166), over n complex elements (dtype
  * TQ_C64 / TQ_C128, t = target, o = the contraction's output, both device):

@@ -29,7 +29,7 @@
 // is monotone, so C is non-decreasing in i, and the bound that selects a chunk for a threshold
 // (Ehi = sbase[g] + cend[c]) is bit-identical to C at the chunk's last element.  FP contraction is
 // off so that both passes round identically whatever the compiler does with either kernel.
-#include "tq_common.h"
+#include "tq_born_common.h"
 
 namespace tq {
 
@@ -40,11 +40,6 @@ constexpr int kBornPL = 16;                      // consecutive elements per lan
 constexpr int kBornChunk = kBornNT * kBornPL;    // 4096
 constexpr int kBornGroup = 16;                   // chunks per group of the base scan
 constexpr int kBornTile = 4 * kBornNT;           // draws tested per round of born_resolve
-constexpr int kBornMaxAxes = 31;
-
-struct BornAxes {
-  int8_t q[kBornMaxAxes + 1];
-};
 
 // workspace layout (all 8-byte words first, then the int32 slab)
 struct BornWs {
@@ -76,15 +71,6 @@ inline BornWs born_ws(void* ws, int64_t n) {
   w.meta = w.sbase + ng + 1;
   w.lastloc = reinterpret_cast<int32_t*>(w.meta + 2);
   return w;
-}
-
-template <typename T>
-__device__ __forceinline__ double born_p(const T* __restrict__ amps, int64_t i) {
-#pragma clang fp contract(off)
-  using R = typename Traits<T>::R;
-  const R* __restrict__ r = reinterpret_cast<const R*>(amps) + 2 * i;
-  const double re = (double)r[0], im = (double)r[1];
-  return re * re + im * im;
 }
 
 // LDS position of chunk element e: one pad word per lane segment, so that lane l reading its
@@ -270,14 +256,6 @@ born_bases(int64_t nchunks, int64_t ngroups, BornWs W, double* __restrict__ stat
   }
 }
 
-__device__ __forceinline__ int64_t born_word(int64_t idx, int n_axes, const BornAxes& ax, uint64_t base) {
-  if (n_axes < 0) return idx;
-  uint64_t wd = base;
-  for (int a = 0; a < n_axes; ++a)
-    wd |= (uint64_t)((idx >> (n_axes - 1 - a)) & 1) << ax.q[a];
-  return (int64_t)wd;
-}
-
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(kBornNT)
 born_resolve(const T* __restrict__ amps, int64_t n, int64_t n_draws, const double* __restrict__ u,
@@ -404,20 +382,7 @@ int born_launch(int dtype, int64_t n, const void* amps, int64_t n_draws, const d
   TQ_CHECK_ARG(((uintptr_t)amps & (ralign - 1)) == 0, "born_sample: misaligned amplitudes");
   BornAxes ax{};
   int na = -1;
-  if (axis_qubit) {
-    TQ_CHECK_ARG(n_axes >= 0 && n_axes <= kBornMaxAxes && n == ((int64_t)1 << n_axes),
-                 "born_sample: n must equal 2^n_axes");
-    uint64_t seen = 0;
-    for (int a = 0; a < n_axes; ++a) {
-      const int q = axis_qubit[a];
-      TQ_CHECK_ARG(q >= 0 && q <= 62, "born_sample: axis qubit outside [0, 62]");
-      TQ_CHECK_ARG(!((seen >> q) & 1), "born_sample: repeated axis qubit");
-      seen |= (uint64_t)1 << q;
-      ax.q[a] = (int8_t)q;
-    }
-    TQ_CHECK_ARG((base & seen) == 0, "born_sample: base overlaps an axis qubit");
-    na = n_axes;
-  }
+  TQ_TRY(born_axes("born_sample", n, n_axes, axis_qubit, base, ax, na));
   const bool vec = ((uintptr_t)amps & 15) == 0;
   if (dtype == TQ_C64)
     return vec ? born_t<c64, true>(n, amps, n_draws, u, index, prob, stats, na, ax, base, workspace, stream)

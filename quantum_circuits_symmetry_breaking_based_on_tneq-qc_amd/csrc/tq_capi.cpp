@@ -555,6 +555,19 @@ int tq_born_sample(int dtype, int64_t n, const void* amps, int64_t n_draws, cons
   TQ_GUARD_END
 }
 
+size_t tq_born_topk_workspace(int dtype, int64_t n, int64_t k) {
+  return tq::born_topk_workspace(dtype, n, k);
+}
+
+int tq_born_topk(int dtype, int64_t n, const void* amps, int64_t k, int64_t* index, double* prob,
+                 int64_t* count, int n_axes, const int32_t* axis_qubit, uint64_t base,
+                 void* workspace, size_t ws_bytes, void* stream) {
+  TQ_GUARD_BEGIN
+  return tq::born_topk_launch(dtype, n, amps, k, index, prob, count, n_axes, axis_qubit, base,
+                              workspace, ws_bytes, (hipStream_t)stream);
+  TQ_GUARD_END
+}
+
 int tq_fidelity_forward(int dtype, int64_t n, const void* t, const void* o, double* stats, void* loss,
                         void* stream) {
   TQ_GUARD_BEGIN

@@ -218,6 +218,11 @@ size_t born_workspace(int dtype, int64_t n, int64_t n_draws);
 int born_launch(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
                 int64_t* index, double* prob, double* stats, int n_axes, const int32_t* axis_qubit,
                 uint64_t base, void* workspace, size_t ws_bytes, hipStream_t stream);
+// the k most probable elements of an amplitude block (tq_topk.hip)
+size_t born_topk_workspace(int dtype, int64_t n, int64_t k);
+int born_topk_launch(int dtype, int64_t n, const void* amps, int64_t k, int64_t* index, double* prob,
+                     int64_t* count, int n_axes, const int32_t* axis_qubit, uint64_t base,
+                     void* workspace, size_t ws_bytes, hipStream_t stream);
 // fidelity loss of the symmetry-breaking fit (tq_loss.hip)
 int fidelity_forward_launch(int dtype, int64_t n, const void* t, const void* o, double* stats, void* loss,
                             hipStream_t stream);

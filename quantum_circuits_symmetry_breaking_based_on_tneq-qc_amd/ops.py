@@ -6,7 +6,8 @@ These are the device primitives the backend and the contraction plans are built 
 BackendPyTorch.einsum with two operands, backend_pytorch.py:623-625), and the measurement-data
 kernels of EngineSiamese: ``hermite_features`` (generate_data, engine_siamese.py:133-254) and
 ``inverse_cdf_sample`` (the CDF block of sample, engine_siamese.py:854-905).  ``born_sample`` has
-no counterpart in the reference: bitstring indices drawn from an amplitude block by the Born rule.
+no counterpart in the reference: bitstring indices drawn from an amplitude block by the Born rule;
+nor has ``born_topk``, the k most probable bitstrings of a block (post-selection).
 """
 from __future__ import annotations
 
@@ -276,6 +277,74 @@ def born_sample(amps: torch.Tensor, u: torch.Tensor, *, prob=True,
                                    ctypes.c_void_p(_stream_ptr(dev)))
     check(rc, "tq_born_sample")
     return out, pr, stats
+
+
+def born_topk_workspace_size(dtype: torch.dtype, n: int, k: int) -> int:
+    """Bytes of device workspace one ``born_topk`` call of these sizes needs (host only)."""
+    wsb = _lib.lib().tq_born_topk_workspace(dtype_code(dtype), int(n), int(k))
+    if wsb == 0:
+        raise ValueError(f"born_topk: {_lib.last_error()}")
+    return int(wsb)
+
+
+def born_topk(amps: torch.Tensor, k: int, *, axis_qubit: Optional[Sequence[int]] = None, base: int = 0,
+              out: Optional[torch.Tensor] = None, prob: Optional[torch.Tensor] = None,
+              count: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """The ``k`` most probable elements of the amplitude block ``amps`` (complex64 / complex128,
+    contiguous, any shape, on the HIP device): the elements with ``p_i = re^2 + im^2 > 0``
+    (float64; +inf counts, NaN and 0 never) ordered by p descending and by index ascending among
+    equal p (include/tneqhip.h, tq_born_topk).  Exact and bitwise reproducible.  Runs on the
+    current stream of ``amps``' device; no host copy, no synchronisation.
+
+    ``axis_qubit`` and ``base`` turn every index into a bitstring word as in ``born_sample``.
+    ``out`` (int64), ``prob`` (float64), both 1-D of exactly ``k`` elements, ``count`` (int64,
+    (1,)) and ``workspace`` (at least ``born_topk_workspace_size`` bytes) are allocated when not
+    given.  Returns ``(index_or_words, prob, count)``: with m = min(k, number of candidates) the
+    first m entries are the selection, the rest is -1 / 0, and ``count[0] = m``."""
+    if not isinstance(amps, torch.Tensor):
+        raise ValueError("born_topk: amps must be a tensor")
+    dev = _require_device(amps)
+    if amps.dtype not in (torch.complex64, torch.complex128):
+        raise ValueError(f"born_topk: amplitudes must be complex64 / complex128, got {amps.dtype}")
+    if not amps.is_contiguous():
+        raise ValueError("born_topk: amplitudes must be contiguous")
+    n, k = amps.numel(), int(k)
+    code = dtype_code(amps.dtype)
+    wsb = born_topk_workspace_size(amps.dtype, n, k)
+
+    def _buf(t, size, dtype, what):
+        if t is None:
+            return torch.empty(size, dtype=dtype, device=dev)
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or t.ndim != 1
+                or not t.is_contiguous() or t.numel() != size):
+            raise ValueError(f"born_topk: {what} must be a contiguous 1-D {dtype} tensor of {size} elements on {dev}")
+        return t
+
+    out = _buf(out, k, torch.int64, "out")
+    prob = _buf(prob, k, torch.float64, "prob")
+    count = _buf(count, 1, torch.int64, "count")
+    if workspace is None:
+        workspace = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("born_topk: workspace must be a contiguous tensor on the amplitudes' device")
+    base = int(base)
+    if not 0 <= base < (1 << 64):
+        raise ValueError("born_topk: base must fit 64 bits")
+    if axis_qubit is not None:
+        axes = [int(q) for q in axis_qubit]
+        if any(not -(1 << 31) <= q < (1 << 31) for q in axes):
+            raise ValueError("born_topk: axis qubit out of range")
+        n_axes, table = len(axes), i32(axes)
+    else:
+        n_axes, table = 0, None
+    rc = _lib.lib().tq_born_topk(code, n, ctypes.c_void_p(amps.data_ptr()), k,
+                                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(prob.data_ptr()),
+                                 ctypes.c_void_p(count.data_ptr()), n_axes, table, base,
+                                 ctypes.c_void_p(workspace.data_ptr()),
+                                 workspace.numel() * workspace.element_size(),
+                                 ctypes.c_void_p(_stream_ptr(dev)))
+    check(rc, "tq_born_topk")
+    return out, prob, count
 
 
 class _FidelityLoss(torch.autograd.Function):

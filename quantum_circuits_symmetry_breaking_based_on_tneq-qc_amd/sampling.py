@@ -32,7 +32,9 @@ written on the slot's stream: `wait()` (current stream waits) or `synchronize()`
 `BlockSampler` is the consumer: a `BlockPipeline` whose every block is followed, on the slot's
 stream, by one Born-rule sampling call (`ops.born_sample`, csrc/tq_born.hip), so `step()` hands
 back bitstring words, their probabilities and the block's mass instead of 8 MB of amplitudes --
-nothing is copied to the host.
+nothing is copied to the host.  `BlockTopK` is the other consumer (post-selection): the same
+pipeline with one top-k call (`tq_born_topk`, csrc/tq_topk.hip) behind every block, handing back the
+k most probable bitstrings of each.
 
 The product path is the native plan only (no CPU fallback): the plans raise when the HIP library
 is missing.
@@ -50,7 +52,7 @@ from ._lib import check
 from .circuits import AmplitudeTask, with_batch
 from .expression import HipContractExpression, run_group
 
-__all__ = ["BlockPipeline", "BlockSampler"]
+__all__ = ["BlockPipeline", "BlockSampler", "BlockTopK"]
 
 
 class _Slot:
@@ -229,6 +231,40 @@ def _word_of(bits) -> int:
     return w
 
 
+def _word_axes(task, who: str) -> List[int]:
+    """The open qubits (one per axis of a block, axis 0 slowest) of a task whose bitstrings fit an
+    int64 word (bit q = qubit q); refuses the others before a device is touched."""
+    qubits = [int(q) for q in task.open_qubits] + [int(q) for q in task.fixed_bits]
+    if len(qubits) > 63 or (qubits and max(qubits) > 62):
+        raise ValueError(f"{who}: {len(qubits)} qubits do not fit a 63-bit bitstring word")
+    return [int(q) for q in task.open_qubits]
+
+
+def _block_bases(task, blocks) -> List[int]:
+    """The closed qubits' bits of every block, as a word: once, not per step."""
+    return [_word_of(with_batch(task, b).fixed_bits) for b in blocks]
+
+
+def _run_consumer(pipe, n: Optional[int]):
+    """`run()` of a pipeline whose `step()` returns a tuple of device tensors: host copies in block
+    order, copied before a slot is reused."""
+    n = len(pipe.blocks) if n is None else n
+    res, pend = [], []
+
+    def drain():
+        pipe.synchronize()
+        res.extend(tuple(t.cpu() for t in o) for o in pend)
+        pend.clear()
+
+    for _ in range(n):
+        pend.append(pipe.step())
+        if pipe.k % pipe.group == 0:
+            drain()
+    if pend:
+        drain()
+    return res
+
+
 class BlockSampler(BlockPipeline):
     """A `BlockPipeline` that samples every block it contracts: `draws` bitstrings per block with
     probability |amplitude|^2 / (block mass), on the device.
@@ -255,9 +291,7 @@ class BlockSampler(BlockPipeline):
     def __init__(self, task: AmplitudeTask, blocks: Sequence[int], draws: int, inflight: int = 2,
                  group: int = 1, device: Optional[torch.device] = None, dtype: torch.dtype = torch.complex64,
                  seed: int = 0, uniforms: Optional[torch.Tensor] = None, min_chunks: Optional[int] = None):
-        qubits = [int(q) for q in task.open_qubits] + [int(q) for q in task.fixed_bits]
-        if len(qubits) > 63 or (qubits and max(qubits) > 62):
-            raise ValueError(f"BlockSampler: {len(qubits)} qubits do not fit a 63-bit bitstring word")
+        axes = _word_axes(task, "BlockSampler")
         draws = int(draws)
         if draws < 1:
             raise ValueError("draws must be >= 1")
@@ -266,9 +300,8 @@ class BlockSampler(BlockPipeline):
         super().__init__(task, blocks, inflight=inflight, group=group, device=device, dtype=dtype,
                          min_chunks=min_chunks)
         self.draws = draws
-        self.axis_qubit = [int(q) for q in task.open_qubits]
-        # the closed qubits' bits of every block, as a word: once, not per step
-        self.base = [_word_of(with_batch(task, b).fixed_bits) for b in self.blocks]
+        self.axis_qubit = axes
+        self.base = _block_bases(task, self.blocks)
         if uniforms is not None:
             if (uniforms.dtype != torch.float64 or uniforms.device != self.device
                     or tuple(uniforms.shape) != (len(self.blocks), draws) or not uniforms.is_contiguous()):
@@ -346,24 +379,102 @@ class BlockSampler(BlockPipeline):
     def run(self, n: Optional[int] = None):
         """Sample the next `n` blocks (default: every block once); returns host copies
         `[(words, prob, stats), ...]` in block order, copied before a slot is reused."""
-        n = len(self.blocks) if n is None else n
-        res, pend = [], []
-
-        def drain():
-            self.synchronize()
-            res.extend(tuple(t.cpu() for t in o) for o in pend)
-            pend.clear()
-
-        for _ in range(n):
-            pend.append(self.step())
-            if self.k % self.group == 0:
-                drain()
-        if pend:
-            drain()
-        return res
+        return _run_consumer(self, n)
 
     def close(self) -> None:
         """Release the pipeline's private plans and the sampler's buffers now."""
         super().close()
         self.sbuf, self.ubuf, self._call = [], [], []
         self.uniforms = None
+
+
+class BlockTopK(BlockPipeline):
+    """A `BlockPipeline` that post-selects every block it contracts: the `k` most probable
+    bitstrings of each block, on the device.
+
+    When a slot's group is launched, one top-k call (`tq_born_topk`, the call under
+    `ops.born_topk`) per member is enqueued on the slot's stream right behind the contraction; it
+    writes into buffers the pipeline owns per (slot, member).  `step()` enqueues the next block
+    and returns that member's `(words, prob, count)` device tensors -- `k` int64 bitstring words
+    (bit q = qubit q: the open qubits from the selected index, the closed ones from the block's
+    fixed bits) in the order |amplitude|^2 descending, index ascending among equal ones; their `k`
+    float64 probabilities; and `count[0]` = how many were selected (a block with fewer than `k`
+    non-zero amplitudes: the rest is words of -1 and probabilities 0).  Like
+    `BlockPipeline.step()`'s outputs they are written when the group has run (`wait()` /
+    `synchronize()`) and overwritten when the slot runs again.  The selection is exact and the
+    same amplitudes give the same bits.  Circuits of more than 63 qubits do not fit the int64
+    words and are refused."""
+
+    def __init__(self, task: AmplitudeTask, blocks: Sequence[int], k: int, inflight: int = 2,
+                 group: int = 1, device: Optional[torch.device] = None, dtype: torch.dtype = torch.complex64,
+                 min_chunks: Optional[int] = None):
+        axes = _word_axes(task, "BlockTopK")
+        k = int(k)
+        if not 1 <= k <= _lib.TQ_BORN_TOPK_MAX_K:
+            raise ValueError(f"BlockTopK: k must be in [1, {_lib.TQ_BORN_TOPK_MAX_K}]")
+        if dtype not in (torch.complex64, torch.complex128):
+            raise ValueError(f"BlockTopK: complex64 / complex128 amplitudes, got {dtype}")
+        super().__init__(task, blocks, inflight=inflight, group=group, device=device, dtype=dtype,
+                         min_chunks=min_chunks)
+        self.topk = k
+        self.axis_qubit = axes
+        self.base = _block_bases(task, self.blocks)
+        n = 2 ** len(self.axis_qubit)
+        wsb = ops.born_topk_workspace_size(dtype, n, k)
+        self.sbuf = []    # [slot][member] -> (words, prob, count, workspace)
+        self._call = []   # [slot][member] -> the constant arguments of tq_born_topk
+        vp = ctypes.c_void_p
+        self._axes = _lib.i32(self.axis_qubit)
+        self._fn = _lib.lib().tq_born_topk
+        for slot in self.slots:
+            bufs = [(torch.empty(k, dtype=torch.int64, device=self.device),
+                     torch.empty(k, dtype=torch.float64, device=self.device),
+                     torch.empty(1, dtype=torch.int64, device=self.device),
+                     torch.empty(wsb, dtype=torch.uint8, device=self.device))
+                    for _ in range(self.group)]
+            self.sbuf.append(bufs)
+            self._call.append([((ops.dtype_code(dtype), n, vp(slot.outs[m].data_ptr()), k,
+                                 vp(b[0].data_ptr()), vp(b[1].data_ptr()), vp(b[2].data_ptr()),
+                                 len(self.axis_qubit), self._axes),
+                                (vp(b[3].data_ptr()), wsb, vp(slot.stream.cuda_stream)))
+                               for m, b in enumerate(bufs)])
+        # one validated call per member (arguments, buffers, the kernels' code objects): the launches
+        # behind the contractions then pass the same arguments straight to the C ABI
+        for s, slot in enumerate(self.slots):
+            with torch.cuda.stream(slot.stream):
+                for m, b in enumerate(self.sbuf[s]):
+                    slot.outs[m].zero_()
+                    ops.born_topk(slot.outs[m], k, axis_qubit=self.axis_qubit, base=self.base[0],
+                                  out=b[0], prob=b[1], count=b[2], workspace=b[3])
+        torch.cuda.synchronize(self.device)
+
+    def _launch(self, slot: _Slot) -> None:
+        rows = list(slot.pending)
+        if not rows:
+            return
+        super()._launch(slot)
+        s = self.slots.index(slot)
+        for m, r in enumerate(rows):
+            head, tail = self._call[s][m]
+            check(self._fn(*head, self.base[r], *tail), "tq_born_topk")
+        slot.event.record(slot.stream)
+
+    def step(self):
+        """Enqueue the next block (as `BlockPipeline.step()`); returns the `(words, prob, count)`
+        device tensors of its (slot, member)."""
+        if self._closed:
+            raise RuntimeError("the pipeline is closed")
+        k = self.k
+        s, m = (k // self.group) % self.inflight, k % self.group
+        super().step()
+        return self.sbuf[s][m][:3]
+
+    def run(self, n: Optional[int] = None):
+        """Select from the next `n` blocks (default: every block once); returns host copies
+        `[(words, prob, count), ...]` in block order, copied before a slot is reused."""
+        return _run_consumer(self, n)
+
+    def close(self) -> None:
+        """Release the pipeline's private plans and the selection buffers now."""
+        super().close()
+        self.sbuf, self._call = [], []
