@@ -294,6 +294,50 @@ int tq_born_sample(int dtype, int64_t n, const void* amps, int64_t n_draws, cons
                    int64_t* index, double* prob, double* stats, int n_axes, const int32_t* axis_qubit,
                    uint64_t base, void* workspace, size_t ws_bytes, void* stream);
 
+/* Born-rule sampling ACROSS blocks: a weighted reservoir of n_draws slots that one call per block
+ * updates, so that after any number of blocks slot j holds a draw from the distribution
+ * p_i / sum over every contributing block (block b with probability S1_b / sum S1, inside it as
+ * tq_born_sample draws).  Slots are independent of each other.
+ * pool (device, 4 float64, read-modify-write) = W (the mass so far), sum S2, the number of blocks
+ * that contributed, the number of slots the last call replaced.  The caller starts a pool by
+ * zeroing all four; an empty (all-zero) pool's reservoir need not be initialised.
+ * tq_born_pool_sample: S1, S2, stats and the candidate (index_j, prob_j) of uniform u[j] are
+ * exactly what tq_born_sample returns for the same amps, u, axis_qubit, base (the same bits, the
+ * same fallback, the same word scatter; the same device functions).  If S1 is not a finite
+ * number > 0 the block contributes nothing: index, prob and pool[0..2] stay as they are and
+ * pool[3] = 0.  Otherwise W' = W + S1 (one float64 add) and slot j is replaced by the candidate
+ * iff W == 0 || v[j] * W' < S1 (one float64 multiply and one compare, no FP contraction: a NaN
+ * v[j] replaces only in an empty pool); other slots are not written; then pool = W', pool[1] + S2,
+ * pool[2] + 1, the count of replaced slots.
+ * u, v: n_draws float64 uniforms each (device); index: n_draws int64; prob: n_draws float64 or
+ * NULL; stats: 2 float64 (all device).  1 <= n <= 2^31, 1 <= n_draws < 2^31.
+ * workspace: tq_born_pool_workspace(dtype, n, n_draws) bytes of device memory, 8-byte aligned
+ * (tq_born_sample's plus 4 bytes per draw and a counter; the query is host-only: 0 and a
+ * tq_last_error message for bad arguments); it need not be zeroed, the call's own kernels zero
+ * what they count in.
+ * tq_born_pool_merge folds reservoir B into A (both n_draws slots): if W_b = pool_b[0] is not a
+ * finite number > 0 nothing changes but pool_a[3] = 0; if W_a == 0 every slot is taken from B;
+ * otherwise W' = W_a + W_b and slot j is taken from B iff v[j] * W' < W_b.  Then pool_a = W',
+ * S2_a + S2_b, blocks_a + blocks_b, the count of slots taken.  B is not modified; prob_a and prob_b
+ * are both NULL or neither; A and B are different buffers.  workspace: at least
+ * TQ_BORN_POOL_MERGE_WORKSPACE bytes, 8-byte aligned (any tq_born_pool_workspace size will do).
+ * Both calls: every argument is checked before anything is launched; nothing is allocated, copied
+ * or synchronised; the launch sequence and the grids depend on (dtype, n, n_draws) only (the data
+ * decides how much a workgroup does, never what is launched: only the chunks that own an accepted
+ * draw read the block a second time); all state lives in device memory, so a captured call
+ * replayed on new amps / u / v contents continues the same pool; no float atomics (the counts
+ * are integer ones), so the same inputs give the same bits; pool is read and written by single
+ * lanes of single-workgroup launches, and the grids read W / W' from the workspace.        */
+#define TQ_BORN_POOL_MERGE_WORKSPACE 64
+size_t tq_born_pool_workspace(int dtype, int64_t n, int64_t n_draws);
+int tq_born_pool_sample(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
+                        const double* v, int64_t* index, double* prob, double* pool, double* stats,
+                        int n_axes, const int32_t* axis_qubit, uint64_t base, void* workspace,
+                        size_t ws_bytes, void* stream);
+int tq_born_pool_merge(int64_t n_draws, const double* v, int64_t* index_a, double* prob_a,
+                       double* pool_a, const int64_t* index_b, const double* prob_b,
+                       const double* pool_b, void* workspace, size_t ws_bytes, void* stream);
+
 /* The k most probable elements of a block of n complex amplitudes (dtype TQ_C64 / TQ_C128,
  * contiguous, device): post-selection, the other consumer of tq_plan_execute's output.  The
  * reference has no counterpart; the nearest thing is EngineSiamese.sample.

@@ -26,8 +26,10 @@ EXPORTED = (
     "tq_plan_profile", "tq_plan_profile_read", "tq_hermite_features", "tq_inverse_cdf_sample",
     "tq_sgdg_step", "tq_fidelity_forward", "tq_fidelity_backward",
     "tq_born_sample_workspace", "tq_born_sample", "tq_born_topk_workspace", "tq_born_topk",
+    "tq_born_pool_workspace", "tq_born_pool_sample", "tq_born_pool_merge",
 )
 TQ_BORN_TOPK_MAX_K = 4096
+TQ_BORN_POOL_MERGE_WORKSPACE = 64
 TQ_SGDG_STIEFEL, TQ_SGDG_BUF_INIT, TQ_SGDG_RETRACT = 1, 2, 4
 TQ_HERMITE_MAX_K, TQ_ICDF_MAX_GRID = 128, 8192
 TQ_OP_PERMUTE, TQ_OP_GEMM, TQ_OP_APPLY, TQ_OP_AXPY, TQ_OP_SWEEP = 0, 1, 2, 3, 4
@@ -87,6 +89,10 @@ _SIGS = {
     "tq_born_sample_workspace": (_c.c_size_t, [_c.c_int, _c.c_int64, _c.c_int64]),
     "tq_born_sample": (_c.c_int, [_c.c_int, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp, _vp, _c.c_int,
                                   _i32p, _c.c_uint64, _vp, _c.c_size_t, _vp]),
+    "tq_born_pool_workspace": (_c.c_size_t, [_c.c_int, _c.c_int64, _c.c_int64]),
+    "tq_born_pool_sample": (_c.c_int, [_c.c_int, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _c.c_int, _i32p, _c.c_uint64, _vp, _c.c_size_t, _vp]),
+    "tq_born_pool_merge": (_c.c_int, [_c.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),
     "tq_born_topk_workspace": (_c.c_size_t, [_c.c_int, _c.c_int64, _c.c_int64]),
     "tq_born_topk": (_c.c_int, [_c.c_int, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp, _c.c_int, _i32p,
                                 _c.c_uint64, _vp, _c.c_size_t, _vp]),

@@ -29,6 +29,9 @@
 // is monotone, so C is non-decreasing in i, and the bound that selects a chunk for a threshold
 // (Ehi = sbase[g] + cend[c]) is bit-identical to C at the chunk's last element.  FP contraction is
 // off so that both passes round identically whatever the compiler does with either kernel.
+//
+// tq_born_pool_sample / tq_born_pool_merge (further down) sample ACROSS blocks with a weighted
+// reservoir; their candidates come from the same chunk_scan, bases_scan and resolve_chunk.
 #include "tq_born_common.h"
 
 namespace tq {
@@ -199,8 +202,9 @@ born_totals(const T* __restrict__ amps, int64_t n, BornWs W) {
   }
 }
 
-__global__ void __launch_bounds__(kBornNT)
-born_bases(int64_t nchunks, int64_t ngroups, BornWs W, double* __restrict__ stats) {
+// The base scan of one workgroup; lane 0 returns S1 and S2 (what it wrote to stats).
+__device__ __forceinline__ void bases_scan(int64_t nchunks, int64_t ngroups, const BornWs& W,
+                                           double* __restrict__ stats, double& S1, double& S2) {
 #pragma clang fp contract(off)
   __shared__ double gt[kBornNT], gs[kBornNT];
   __shared__ int64_t gl[kBornNT];
@@ -254,13 +258,26 @@ born_bases(int64_t nchunks, int64_t ngroups, BornWs W, double* __restrict__ stat
     stats[0] = acc0;
     stats[1] = s20;
   }
+  S1 = acc0;
+  S2 = s20;
 }
 
-template <typename T, bool VEC>
 __global__ void __launch_bounds__(kBornNT)
-born_resolve(const T* __restrict__ amps, int64_t n, int64_t n_draws, const double* __restrict__ u,
-             int64_t* __restrict__ index, double* __restrict__ prob, BornWs W, int n_axes,
-             BornAxes ax, uint64_t base) {
+born_bases(int64_t nchunks, int64_t ngroups, BornWs W, double* __restrict__ stats) {
+  double S1, S2;
+  bases_scan(nchunks, ngroups, W, stats, S1, S2);
+}
+
+// The resolve step of chunk blockIdx.x over `n_items` draws.  SEL = false (tq_born_sample): item s
+// is draw s.  SEL = true (tq_born_pool_sample): item s is draw sel[s], the accepted draws of the
+// call in any order; only those slots of index / prob are written, and a block without mass
+// writes nothing (its list is empty).
+template <typename T, bool VEC, bool SEL>
+__device__ __forceinline__ void resolve_chunk(const T* __restrict__ amps, int64_t n, int64_t n_items,
+                                              const double* __restrict__ u, const int32_t* __restrict__ sel,
+                                              int64_t* __restrict__ index, double* __restrict__ prob,
+                                              const BornWs& W, int n_axes, const BornAxes& ax,
+                                              uint64_t base) {
 #pragma clang fp contract(off)
   __shared__ BornLds L;
   __shared__ int list[kBornTile];
@@ -269,11 +286,13 @@ born_resolve(const T* __restrict__ amps, int64_t n, int64_t n_draws, const doubl
   const int64_t c = blockIdx.x;
   const double S1 = W.meta[0];
   if (!(S1 > 0.0 && S1 < __builtin_huge_val())) {
-    if (c == 0)
-      for (int64_t j = tid; j < n_draws; j += kBornNT) {
-        index[j] = -1;
-        if (prob) prob[j] = 0.0;
-      }
+    if constexpr (!SEL) {
+      if (c == 0)
+        for (int64_t j = tid; j < n_items; j += kBornNT) {
+          index[j] = -1;
+          if (prob) prob[j] = 0.0;
+        }
+    }
     return;
   }
   const int64_t g = c / kBornGroup;
@@ -285,14 +304,16 @@ born_resolve(const T* __restrict__ amps, int64_t n, int64_t n_draws, const doubl
   if (tid == 0) cnt = 0;
   __syncthreads();
   bool scanned = false;
-  for (int64_t j0 = 0; j0 < n_draws; j0 += kBornTile) {
+  for (int64_t j0 = 0; j0 < n_items; j0 += kBornTile) {
 #pragma unroll
     for (int q = 0; q < kBornTile / kBornNT; ++q) {
-      const int64_t j = j0 + q * kBornNT + tid;
-      if (j < n_draws) {
+      const int64_t s = j0 + q * kBornNT + tid;
+      if (s < n_items) {
+        int64_t j = s;
+        if constexpr (SEL) j = sel[s];
         const double t = u[j] * S1;
         if (Ehi > t && (c == 0 || !(Elo > t))) {
-          list[atomicAdd(&cnt, 1)] = (int)(j - j0);
+          list[atomicAdd(&cnt, 1)] = (int)(s - j0);
         } else if (c == 0 && !(S1 > t)) {
           // no C_i exceeds t (u >= 1, NaN, rounding): the last element with p > 0
           index[j] = lastpos >= 0 ? born_word(lastpos, n_axes, ax, base) : -1;
@@ -311,7 +332,8 @@ born_resolve(const T* __restrict__ amps, int64_t n, int64_t n_draws, const doubl
         scanned = true;
       }
       for (int s = tid; s < m; s += kBornNT) {
-        const int64_t j = j0 + list[s];
+        int64_t j = j0 + list[s];
+        if constexpr (SEL) j = sel[j];
         const double t = u[j] * S1;
         // first i with C_i > t; C at the chunk's last element is Ehi > t
         int lo = 0, hi = kBornChunk - 1;
@@ -330,6 +352,153 @@ born_resolve(const T* __restrict__ amps, int64_t n, int64_t n_draws, const doubl
     if (tid == 0) cnt = 0;
     __syncthreads();
   }
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kBornNT)
+born_resolve(const T* __restrict__ amps, int64_t n, int64_t n_draws, const double* __restrict__ u,
+             int64_t* __restrict__ index, double* __restrict__ prob, BornWs W, int n_axes,
+             BornAxes ax, uint64_t base) {
+  resolve_chunk<T, VEC, false>(amps, n, n_draws, u, nullptr, index, prob, W, n_axes, ax, base);
+}
+
+// ---- the pool: a weighted reservoir over blocks (tq_born_pool_sample / tq_born_pool_merge) -------
+//
+// Four launches per block, the first unchanged: born_totals, born_pool_bases (born_bases' scan,
+// then lane 0 reads the pool, decides whether the block contributes, leaves W, W', S1 and that flag
+// in the workspace, zeroes the accepted counter and updates pool[0..2]), born_pool_accept (a grid
+// over the draws: the acceptance rule, accepted j appended to a list), born_pool_resolve
+// (resolve_chunk over that list; workgroup 0 writes the count to pool[3]).  Every grid that needs
+// W / W' reads the workspace copy, written one launch earlier by one workgroup; pool itself is read
+// and written by that workgroup's lane 0 only, and pool[3] by one lane of the last launch.
+
+struct PoolWs {
+  double* pm;        // [0] = W before, [1] = W', [2] = S1 (sample) / W_b (merge), [3] = 0 no-op, 1 rule, 2 all
+  int32_t* count;    // accepted / taken slots (8 bytes reserved)
+  int32_t* list;     // [n_draws] accepted draws (sample only)
+};
+
+constexpr size_t kPoolHead = 4 * 8 + 8;
+
+inline size_t born_pool_ws_bytes(int64_t n, int64_t n_draws) {
+  return (born_ws_bytes(n) + kPoolHead + (size_t)n_draws * 4 + 15) & ~(size_t)15;
+}
+
+inline PoolWs pool_ws(void* at) {
+  PoolWs p;
+  p.pm = reinterpret_cast<double*>(at);
+  p.count = reinterpret_cast<int32_t*>(p.pm + 4);
+  p.list = p.count + 2;
+  return p;
+}
+
+__device__ __forceinline__ bool born_mass(double x) { return x > 0.0 && x < __builtin_huge_val(); }
+
+__global__ void __launch_bounds__(kBornNT)
+born_pool_bases(int64_t nchunks, int64_t ngroups, BornWs W, double* __restrict__ stats,
+                double* __restrict__ pool, PoolWs P) {
+#pragma clang fp contract(off)
+  double S1, S2;
+  bases_scan(nchunks, ngroups, W, stats, S1, S2);
+  if (threadIdx.x == 0) {
+    const double w0 = pool[0];
+    const bool ok = born_mass(S1);
+    const double w1 = w0 + S1;
+    P.pm[0] = w0;
+    P.pm[1] = w1;
+    P.pm[2] = S1;
+    P.pm[3] = !ok ? 0.0 : (w0 == 0.0 ? 2.0 : 1.0);
+    *P.count = 0;
+    if (ok) {
+      pool[0] = w1;
+      pool[1] = pool[1] + S2;
+      pool[2] = pool[2] + 1.0;
+    }
+  }
+}
+
+// take(j): pm[3] == 2, or pm[3] == 1 and v_j * W' < mass (one multiply, one compare; NaN: false)
+__device__ __forceinline__ bool pool_take(const PoolWs& P, const double* __restrict__ v, int64_t j) {
+#pragma clang fp contract(off)
+  const double mode = P.pm[3];
+  if (mode == 0.0) return false;
+  if (mode == 2.0) return true;
+  return v[j] * P.pm[1] < P.pm[2];
+}
+
+__global__ void __launch_bounds__(kBornNT)
+born_pool_accept(int64_t n_draws, const double* __restrict__ v, PoolWs P) {
+  const int64_t j = (int64_t)blockIdx.x * kBornNT + threadIdx.x;
+  if (j < n_draws && pool_take(P, v, j)) P.list[atomicAdd(P.count, 1)] = (int32_t)j;
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(kBornNT)
+born_pool_resolve(const T* __restrict__ amps, int64_t n, const double* __restrict__ u,
+                  int64_t* __restrict__ index, double* __restrict__ prob, double* __restrict__ pool,
+                  BornWs W, PoolWs P, int n_axes, BornAxes ax, uint64_t base) {
+  const int64_t m = *P.count;
+  if (blockIdx.x == 0 && threadIdx.x == 0) pool[3] = (double)m;
+  if (m == 0) return;   // before anything of the block is read
+  resolve_chunk<T, VEC, true>(amps, n, m, u, P.list, index, prob, W, n_axes, ax, base);
+}
+
+__global__ void born_merge_head(const double* __restrict__ pool_a, const double* __restrict__ pool_b,
+                                PoolWs P) {
+#pragma clang fp contract(off)
+  if (threadIdx.x == 0) {
+    const double wa = pool_a[0], wb = pool_b[0];
+    P.pm[0] = wa;
+    P.pm[1] = wa + wb;
+    P.pm[2] = wb;
+    P.pm[3] = !born_mass(wb) ? 0.0 : (wa == 0.0 ? 2.0 : 1.0);
+    *P.count = 0;
+  }
+}
+
+__global__ void __launch_bounds__(kBornNT)
+born_merge_take(int64_t n_draws, const double* __restrict__ v, int64_t* __restrict__ index_a,
+                double* __restrict__ prob_a, const int64_t* __restrict__ index_b,
+                const double* __restrict__ prob_b, PoolWs P) {
+  const int64_t j = (int64_t)blockIdx.x * kBornNT + threadIdx.x;
+  if (j < n_draws && pool_take(P, v, j)) {
+    index_a[j] = index_b[j];
+    if (prob_a) prob_a[j] = prob_b[j];
+    atomicAdd(P.count, 1);
+  }
+}
+
+__global__ void born_merge_tail(double* __restrict__ pool_a, const double* __restrict__ pool_b, PoolWs P) {
+#pragma clang fp contract(off)
+  if (threadIdx.x == 0) {
+    if (P.pm[3] != 0.0) {
+      pool_a[0] = P.pm[1];
+      pool_a[1] = pool_a[1] + pool_b[1];
+      pool_a[2] = pool_a[2] + pool_b[2];
+    }
+    pool_a[3] = (double)*P.count;
+  }
+}
+
+template <typename T, bool VEC>
+int born_pool_t(int64_t n, const void* amps, int64_t n_draws, const double* u, const double* v,
+                int64_t* index, double* prob, double* pool, double* stats, int n_axes,
+                const BornAxes& ax, uint64_t base, void* ws, hipStream_t st) {
+  const int64_t nc = born_chunks(n), ng = born_groups(nc);
+  const BornWs W = born_ws(ws, n);
+  const PoolWs P = pool_ws(reinterpret_cast<char*>(ws) + born_ws_bytes(n));
+  const T* a = reinterpret_cast<const T*>(amps);
+  hipLaunchKernelGGL((born_totals<T, VEC>), dim3((unsigned)nc), dim3(kBornNT), 0, st, a, n, W);
+  TQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(born_pool_bases, dim3(1), dim3(kBornNT), 0, st, nc, ng, W, stats, pool, P);
+  TQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(born_pool_accept, dim3((unsigned)((n_draws + kBornNT - 1) / kBornNT)), dim3(kBornNT),
+                     0, st, n_draws, v, P);
+  TQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL((born_pool_resolve<T, VEC>), dim3((unsigned)nc), dim3(kBornNT), 0, st, a, n, u,
+                     index, prob, pool, W, P, n_axes, ax, base);
+  TQ_HIP(hipGetLastError());
+  return TQ_OK;
 }
 
 template <typename T, bool VEC>
@@ -389,6 +558,65 @@ int born_launch(int dtype, int64_t n, const void* amps, int64_t n_draws, const d
                : born_t<c64, false>(n, amps, n_draws, u, index, prob, stats, na, ax, base, workspace, stream);
   return vec ? born_t<c128, true>(n, amps, n_draws, u, index, prob, stats, na, ax, base, workspace, stream)
              : born_t<c128, false>(n, amps, n_draws, u, index, prob, stats, na, ax, base, workspace, stream);
+}
+
+size_t born_pool_workspace(int dtype, int64_t n, int64_t n_draws) {
+  if (dtype != TQ_C64 && dtype != TQ_C128) {
+    set_error("born_pool: amplitudes must be TQ_C64 or TQ_C128");
+    return 0;
+  }
+  if (n < 1 || n > ((int64_t)1 << 31)) {
+    set_error("born_pool: n must be in [1, 2^31]");
+    return 0;
+  }
+  if (n_draws < 1 || n_draws >= ((int64_t)1 << 31)) {
+    set_error("born_pool: n_draws must be in [1, 2^31)");
+    return 0;
+  }
+  return born_pool_ws_bytes(n, n_draws);
+}
+
+int born_pool_launch(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
+                     const double* v, int64_t* index, double* prob, double* pool, double* stats,
+                     int n_axes, const int32_t* axis_qubit, uint64_t base, void* workspace,
+                     size_t ws_bytes, hipStream_t stream) {
+  const size_t need = born_pool_workspace(dtype, n, n_draws);
+  if (need == 0) return TQ_ERR_INVALID;
+  TQ_CHECK_ARG(amps && u && v && index && pool && stats && workspace, "born_pool: null pointer");
+  TQ_CHECK_ARG(ws_bytes >= need, "born_pool: workspace smaller than tq_born_pool_workspace");
+  TQ_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "born_pool: workspace must be 8-byte aligned");
+  const size_t ralign = dtype == TQ_C64 ? 4 : 8;
+  TQ_CHECK_ARG(((uintptr_t)amps & (ralign - 1)) == 0, "born_pool: misaligned amplitudes");
+  BornAxes ax{};
+  int na = -1;
+  TQ_TRY(born_axes("born_pool", n, n_axes, axis_qubit, base, ax, na));
+  const bool vec = ((uintptr_t)amps & 15) == 0;
+  if (dtype == TQ_C64)
+    return vec ? born_pool_t<c64, true>(n, amps, n_draws, u, v, index, prob, pool, stats, na, ax, base, workspace, stream)
+               : born_pool_t<c64, false>(n, amps, n_draws, u, v, index, prob, pool, stats, na, ax, base, workspace, stream);
+  return vec ? born_pool_t<c128, true>(n, amps, n_draws, u, v, index, prob, pool, stats, na, ax, base, workspace, stream)
+             : born_pool_t<c128, false>(n, amps, n_draws, u, v, index, prob, pool, stats, na, ax, base, workspace, stream);
+}
+
+int born_pool_merge_launch(int64_t n_draws, const double* v, int64_t* index_a, double* prob_a,
+                           double* pool_a, const int64_t* index_b, const double* prob_b,
+                           const double* pool_b, void* workspace, size_t ws_bytes, hipStream_t stream) {
+  TQ_CHECK_ARG(n_draws >= 1 && n_draws < ((int64_t)1 << 31), "born_pool: n_draws must be in [1, 2^31)");
+  TQ_CHECK_ARG(v && index_a && pool_a && index_b && pool_b && workspace, "born_pool: null pointer");
+  TQ_CHECK_ARG((prob_a == nullptr) == (prob_b == nullptr), "born_pool: prob_a and prob_b are both NULL or neither");
+  static_assert(kPoolHead <= TQ_BORN_POOL_MERGE_WORKSPACE, "the merge uses the head of the pool workspace");
+  TQ_CHECK_ARG(ws_bytes >= TQ_BORN_POOL_MERGE_WORKSPACE, "born_pool: merge workspace smaller than TQ_BORN_POOL_MERGE_WORKSPACE");
+  TQ_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "born_pool: workspace must be 8-byte aligned");
+  TQ_CHECK_ARG(index_a != index_b && pool_a != pool_b, "born_pool: a reservoir cannot be merged into itself");
+  const PoolWs P = pool_ws(workspace);
+  hipLaunchKernelGGL(born_merge_head, dim3(1), dim3(64), 0, stream, pool_a, pool_b, P);
+  TQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(born_merge_take, dim3((unsigned)((n_draws + kBornNT - 1) / kBornNT)), dim3(kBornNT),
+                     0, stream, n_draws, v, index_a, prob_a, index_b, prob_b, P);
+  TQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(born_merge_tail, dim3(1), dim3(64), 0, stream, pool_a, pool_b, P);
+  TQ_HIP(hipGetLastError());
+  return TQ_OK;
 }
 
 }  // namespace tq

@@ -555,6 +555,29 @@ int tq_born_sample(int dtype, int64_t n, const void* amps, int64_t n_draws, cons
   TQ_GUARD_END
 }
 
+size_t tq_born_pool_workspace(int dtype, int64_t n, int64_t n_draws) {
+  return tq::born_pool_workspace(dtype, n, n_draws);
+}
+
+int tq_born_pool_sample(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
+                        const double* v, int64_t* index, double* prob, double* pool, double* stats,
+                        int n_axes, const int32_t* axis_qubit, uint64_t base, void* workspace,
+                        size_t ws_bytes, void* stream) {
+  TQ_GUARD_BEGIN
+  return tq::born_pool_launch(dtype, n, amps, n_draws, u, v, index, prob, pool, stats, n_axes,
+                              axis_qubit, base, workspace, ws_bytes, (hipStream_t)stream);
+  TQ_GUARD_END
+}
+
+int tq_born_pool_merge(int64_t n_draws, const double* v, int64_t* index_a, double* prob_a,
+                       double* pool_a, const int64_t* index_b, const double* prob_b,
+                       const double* pool_b, void* workspace, size_t ws_bytes, void* stream) {
+  TQ_GUARD_BEGIN
+  return tq::born_pool_merge_launch(n_draws, v, index_a, prob_a, pool_a, index_b, prob_b, pool_b,
+                                    workspace, ws_bytes, (hipStream_t)stream);
+  TQ_GUARD_END
+}
+
 size_t tq_born_topk_workspace(int dtype, int64_t n, int64_t k) {
   return tq::born_topk_workspace(dtype, n, k);
 }

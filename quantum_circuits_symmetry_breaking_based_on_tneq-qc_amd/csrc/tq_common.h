@@ -218,6 +218,15 @@ size_t born_workspace(int dtype, int64_t n, int64_t n_draws);
 int born_launch(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
                 int64_t* index, double* prob, double* stats, int n_axes, const int32_t* axis_qubit,
                 uint64_t base, void* workspace, size_t ws_bytes, hipStream_t stream);
+// ... and across blocks: the weighted reservoir (tq_born.hip)
+size_t born_pool_workspace(int dtype, int64_t n, int64_t n_draws);
+int born_pool_launch(int dtype, int64_t n, const void* amps, int64_t n_draws, const double* u,
+                     const double* v, int64_t* index, double* prob, double* pool, double* stats,
+                     int n_axes, const int32_t* axis_qubit, uint64_t base, void* workspace,
+                     size_t ws_bytes, hipStream_t stream);
+int born_pool_merge_launch(int64_t n_draws, const double* v, int64_t* index_a, double* prob_a,
+                           double* pool_a, const int64_t* index_b, const double* prob_b,
+                           const double* pool_b, void* workspace, size_t ws_bytes, hipStream_t stream);
 // the k most probable elements of an amplitude block (tq_topk.hip)
 size_t born_topk_workspace(int dtype, int64_t n, int64_t k);
 int born_topk_launch(int dtype, int64_t n, const void* amps, int64_t k, int64_t* index, double* prob,

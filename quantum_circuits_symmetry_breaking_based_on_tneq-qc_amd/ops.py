@@ -7,7 +7,8 @@ BackendPyTorch.einsum with two operands, backend_pytorch.py:623-625), and the me
 kernels of EngineSiamese: ``hermite_features`` (generate_data, engine_siamese.py:133-254) and
 ``inverse_cdf_sample`` (the CDF block of sample, engine_siamese.py:854-905).  ``born_sample`` has
 no counterpart in the reference: bitstring indices drawn from an amplitude block by the Born rule;
-nor has ``born_topk``, the k most probable bitstrings of a block (post-selection).
+nor has ``born_topk``, the k most probable bitstrings of a block (post-selection), nor
+``born_pool_sample`` / ``born_pool_merge``, the weighted reservoir that samples across blocks.
 """
 from __future__ import annotations
 
@@ -277,6 +278,127 @@ def born_sample(amps: torch.Tensor, u: torch.Tensor, *, prob=True,
                                    ctypes.c_void_p(_stream_ptr(dev)))
     check(rc, "tq_born_sample")
     return out, pr, stats
+
+
+def born_pool_workspace_size(dtype: torch.dtype, n: int, n_draws: int) -> int:
+    """Bytes of device workspace one ``born_pool_sample`` call of these sizes needs (host only)."""
+    wsb = _lib.lib().tq_born_pool_workspace(dtype_code(dtype), int(n), int(n_draws))
+    if wsb == 0:
+        raise ValueError(f"born_pool_sample: {_lib.last_error()}")
+    return int(wsb)
+
+
+def _pool_buf(who, t, size, dtype, what, dev):
+    if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or t.ndim != 1
+            or not t.is_contiguous() or t.numel() != size):
+        raise ValueError(f"{who}: {what} must be a contiguous 1-D {dtype} tensor of {size} elements on {dev}")
+    return t
+
+
+def born_pool_sample(amps: torch.Tensor, u: torch.Tensor, v: torch.Tensor, index: torch.Tensor,
+                     prob: Optional[torch.Tensor], pool: torch.Tensor, *,
+                     axis_qubit: Optional[Sequence[int]] = None, base: int = 0,
+                     stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Fold the amplitude block ``amps`` into the weighted reservoir ``(index, prob, pool)`` of
+    ``len(u)`` slots (include/tneqhip.h, tq_born_pool_sample): the block's candidate for slot j is
+    what ``born_sample`` draws for ``u[j]``, and it replaces the slot iff the pool is empty or
+    ``v[j] * (W + S1) < S1``, so that after any number of blocks every slot is a Born-rule draw
+    over all of them.  ``pool`` (float64, (4,)) = W, sum S2, blocks that contributed, slots the
+    last call replaced; zero it to start a pool.  A block whose mass is not a finite number > 0
+    changes nothing but ``pool[3] = 0``.  Runs on the current stream of ``amps``' device; no host
+    copy, no synchronisation.
+
+    ``u``, ``v``: float64 uniforms, 1-D, the same length >= 1; ``index`` (int64) and ``prob``
+    (float64, or None: no probabilities) have exactly that length and are updated in place.
+    ``axis_qubit`` and ``base`` turn every index into a bitstring word as in ``born_sample``.
+    ``stats`` (float64, (2,)) and ``workspace`` (at least ``born_pool_workspace_size`` bytes) are
+    allocated when not given.  Returns ``(index, prob, pool, stats)``; stats = this block's
+    (S1, sum p^2)."""
+    who = "born_pool_sample"
+    if not all(isinstance(t, torch.Tensor) for t in (amps, u, v)):
+        raise ValueError(f"{who}: amps, u and v must be tensors")
+    dev = _require_device(amps)
+    if amps.dtype not in (torch.complex64, torch.complex128):
+        raise ValueError(f"{who}: amplitudes must be complex64 / complex128, got {amps.dtype}")
+    if not amps.is_contiguous():
+        raise ValueError(f"{who}: amplitudes must be contiguous")
+    if not isinstance(u, torch.Tensor) or u.ndim != 1 or u.numel() < 1:
+        raise ValueError(f"{who}: u must be a 1-D tensor of at least one uniform")
+    n, nd = amps.numel(), u.numel()
+    code = dtype_code(amps.dtype)
+    wsb = born_pool_workspace_size(amps.dtype, n, nd)
+    _pool_buf(who, u, nd, torch.float64, "u", dev)
+    _pool_buf(who, v, nd, torch.float64, "v", dev)
+    _pool_buf(who, index, nd, torch.int64, "index", dev)
+    if prob is not None:
+        _pool_buf(who, prob, nd, torch.float64, "prob", dev)
+    _pool_buf(who, pool, 4, torch.float64, "pool", dev)
+    if stats is None:
+        stats = torch.empty(2, dtype=torch.float64, device=dev)
+    else:
+        _pool_buf(who, stats, 2, torch.float64, "stats", dev)
+    if workspace is None:
+        workspace = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"{who}: workspace must be a contiguous tensor on the amplitudes' device")
+    base = int(base)
+    if not 0 <= base < (1 << 64):
+        raise ValueError(f"{who}: base must fit 64 bits")
+    if axis_qubit is not None:
+        axes = [int(q) for q in axis_qubit]
+        if any(not -(1 << 31) <= q < (1 << 31) for q in axes):
+            raise ValueError(f"{who}: axis qubit out of range")
+        n_axes, table = len(axes), i32(axes)
+    else:
+        n_axes, table = 0, None
+    vp = ctypes.c_void_p
+    rc = _lib.lib().tq_born_pool_sample(code, n, vp(amps.data_ptr()), nd, vp(u.data_ptr()), vp(v.data_ptr()),
+                                        vp(index.data_ptr()), vp(prob.data_ptr() if prob is not None else None),
+                                        vp(pool.data_ptr()), vp(stats.data_ptr()), n_axes, table, base,
+                                        vp(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+                                        vp(_stream_ptr(dev)))
+    check(rc, "tq_born_pool_sample")
+    return index, prob, pool, stats
+
+
+def born_pool_merge(index_a: torch.Tensor, prob_a: Optional[torch.Tensor], pool_a: torch.Tensor,
+                    index_b: torch.Tensor, prob_b: Optional[torch.Tensor], pool_b: torch.Tensor,
+                    v: torch.Tensor, *, workspace: Optional[torch.Tensor] = None):
+    """Fold reservoir B into reservoir A in place (include/tneqhip.h, tq_born_pool_merge): slot j is
+    taken from B iff A is empty or ``v[j] * (W_a + W_b) < W_b``; ``pool_a`` becomes the sums and the
+    number of slots taken.  An empty B (``pool_b[0]`` not a finite number > 0) changes nothing but
+    ``pool_a[3] = 0``; B is never modified.  ``prob_a`` and ``prob_b`` are both None or neither.
+    ``workspace``: at least ``TQ_BORN_POOL_MERGE_WORKSPACE`` (64) bytes, allocated when not given.
+    Runs on the current stream of A's device.  Returns ``(index_a, prob_a, pool_a)``."""
+    who = "born_pool_merge"
+    if not isinstance(index_a, torch.Tensor):
+        raise ValueError(f"{who}: index_a must be a tensor")
+    dev = _require_device(index_a)
+    nd = index_a.numel()
+    if index_a.ndim != 1 or nd < 1:
+        raise ValueError(f"{who}: index_a must be a 1-D tensor of at least one slot")
+    if (prob_a is None) != (prob_b is None):
+        raise ValueError(f"{who}: prob_a and prob_b are both None or neither")
+    _pool_buf(who, index_a, nd, torch.int64, "index_a", dev)
+    _pool_buf(who, index_b, nd, torch.int64, "index_b", dev)
+    if prob_a is not None:
+        _pool_buf(who, prob_a, nd, torch.float64, "prob_a", dev)
+        _pool_buf(who, prob_b, nd, torch.float64, "prob_b", dev)
+    _pool_buf(who, pool_a, 4, torch.float64, "pool_a", dev)
+    _pool_buf(who, pool_b, 4, torch.float64, "pool_b", dev)
+    _pool_buf(who, v, nd, torch.float64, "v", dev)
+    if workspace is None:
+        workspace = torch.empty(_lib.TQ_BORN_POOL_MERGE_WORKSPACE, dtype=torch.uint8, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"{who}: workspace must be a contiguous tensor on the reservoirs' device")
+    vp = ctypes.c_void_p
+    rc = _lib.lib().tq_born_pool_merge(nd, vp(v.data_ptr()), vp(index_a.data_ptr()),
+                                       vp(prob_a.data_ptr() if prob_a is not None else None), vp(pool_a.data_ptr()),
+                                       vp(index_b.data_ptr()), vp(prob_b.data_ptr() if prob_b is not None else None),
+                                       vp(pool_b.data_ptr()), vp(workspace.data_ptr()),
+                                       workspace.numel() * workspace.element_size(), vp(_stream_ptr(dev)))
+    check(rc, "tq_born_pool_merge")
+    return index_a, prob_a, pool_a
 
 
 def born_topk_workspace_size(dtype: torch.dtype, n: int, k: int) -> int:

@@ -34,7 +34,9 @@ stream, by one Born-rule sampling call (`ops.born_sample`, csrc/tq_born.hip), so
 back bitstring words, their probabilities and the block's mass instead of 8 MB of amplitudes --
 nothing is copied to the host.  `BlockTopK` is the other consumer (post-selection): the same
 pipeline with one top-k call (`tq_born_topk`, csrc/tq_topk.hip) behind every block, handing back the
-k most probable bitstrings of each.
+k most probable bitstrings of each.  `PoolSampler` samples ACROSS the blocks: one weighted
+reservoir per slot that every block of the slot is folded into (`tq_born_pool_sample`), merged by
+`result()` (`tq_born_pool_merge`) into draws from the distribution over everything contracted.
 
 The product path is the native plan only (no CPU fallback): the plans raise when the HIP library
 is missing.
@@ -52,7 +54,7 @@ from ._lib import check
 from .circuits import AmplitudeTask, with_batch
 from .expression import HipContractExpression, run_group
 
-__all__ = ["BlockPipeline", "BlockSampler", "BlockTopK"]
+__all__ = ["BlockPipeline", "BlockSampler", "BlockTopK", "PoolSampler"]
 
 
 class _Slot:
@@ -284,8 +286,8 @@ class BlockSampler(BlockPipeline):
     without it they are drawn at launch time from a `torch.Generator` of the device seeded with
     `seed` (the same seed and the same call sequence give the same words).
 
-    Every block gets the same number of draws: choosing WHICH block to sample, in proportion to
-    the blocks' masses, is the caller's business -- `stats[0]` is the mass they need for it.
+    Every block gets the same number of draws: `PoolSampler` is the sampler that chooses WHICH
+    block a draw comes from, in proportion to the blocks' masses (`stats[0]` here).
     Circuits of more than 63 qubits do not fit the int64 words and are refused."""
 
     def __init__(self, task: AmplitudeTask, blocks: Sequence[int], draws: int, inflight: int = 2,
@@ -478,3 +480,179 @@ class BlockTopK(BlockPipeline):
         """Release the pipeline's private plans and the selection buffers now."""
         super().close()
         self.sbuf, self._call = [], []
+
+
+class PoolSampler(BlockPipeline):
+    """A `BlockPipeline` that samples across the blocks it contracts: `draws` bitstrings from the
+    Born distribution over EVERY block stepped so far, |amplitude|^2 / (sum of the blocks'
+    masses), on the device.  The block boundary does not reach the caller.
+
+    Every slot holds a weighted reservoir `(words, prob, pool)` of `draws` slots.  When a slot's
+    group is launched, one `tq_born_pool_sample` call per member (in member order) is enqueued on
+    the slot's stream right behind the contraction: block b of mass S1_b replaces reservoir slot j
+    by its own Born-rule draw j with probability S1_b / (W + S1_b), W the mass the reservoir has
+    seen (include/tneqhip.h).  After any number of blocks slot j holds a draw from block b with
+    probability S1_b / sum S1 and, inside it, bitstring i with p_i / S1_b: p_i / sum, the Born rule
+    over the pool.  Only the accepted draws (about draws / k of the k-th block) are resolved.
+
+    `step()` enqueues the next block and returns None: there is no per-block result.  `result()`
+    merges the slots' reservoirs (`tq_born_pool_merge`) and returns `(words, prob, pool)`.
+
+    Uniforms: `uniforms` is a contiguous `(len(blocks), 2, draws)` float64 device tensor; row
+    `[k, 0]` is `u` (the draw inside block k) and `[k, 1]` is `v` (the acceptance) of block k.
+    Without it both come from a `torch.Generator` of the device seeded with `seed` (the same seed
+    and the same call sequence give the same words).  Circuits of more than 63 qubits do not fit
+    the int64 words and are refused."""
+
+    def __init__(self, task: AmplitudeTask, blocks: Sequence[int], draws: int, inflight: int = 2,
+                 group: int = 1, device: Optional[torch.device] = None, dtype: torch.dtype = torch.complex64,
+                 seed: int = 0, uniforms: Optional[torch.Tensor] = None, min_chunks: Optional[int] = None):
+        axes = _word_axes(task, "PoolSampler")
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError("draws must be >= 1")
+        if dtype not in (torch.complex64, torch.complex128):
+            raise ValueError(f"PoolSampler: complex64 / complex128 amplitudes, got {dtype}")
+        super().__init__(task, blocks, inflight=inflight, group=group, device=device, dtype=dtype,
+                         min_chunks=min_chunks)
+        self.draws = draws
+        self.axis_qubit = axes
+        self.base = _block_bases(task, self.blocks)
+        if uniforms is not None:
+            if (uniforms.dtype != torch.float64 or uniforms.device != self.device
+                    or tuple(uniforms.shape) != (len(self.blocks), 2, draws) or not uniforms.is_contiguous()):
+                raise ValueError(f"uniforms must be a contiguous ({len(self.blocks)}, 2, {draws}) float64 tensor on {self.device}")
+            self.gen = None
+        else:
+            self.gen = torch.Generator(self.device)
+            self.gen.manual_seed(int(seed))
+        self._seed, self._mgen = int(seed), None
+        self.uniforms = uniforms
+        n = 2 ** len(self.axis_qubit)
+        wsb = ops.born_pool_workspace_size(dtype, n, draws)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        # generated uniforms: one refill of `_refill` launches' worth per slot, on the slot's stream
+        self._refill = 16
+        self.rbuf = []    # [slot] -> (words, prob, pool, workspace): the slot's reservoir
+        self.sstat = []   # [slot][member] -> the member's last block's (S1, S2)
+        self.ubuf = []    # [slot] -> (_refill, group, 2, draws) uniforms, or None
+        self._ucur = []   # [slot] -> launches served from the slot's current refill
+        self._call = []   # [slot][member] -> the constant arguments of tq_born_pool_sample
+        vp = ctypes.c_void_p
+        self._axes = _lib.i32(self.axis_qubit)
+        self._fn = _lib.lib().tq_born_pool_sample
+        for slot in self.slots:
+            r = (torch.full((draws,), -1, dtype=torch.int64, device=self.device), torch.zeros(draws, **f64),
+                 torch.zeros(4, **f64), torch.empty(wsb, dtype=torch.uint8, device=self.device))
+            st = [torch.empty(2, **f64) for _ in range(self.group)]
+            self.rbuf.append(r)
+            self.sstat.append(st)
+            self.ubuf.append(torch.empty((self._refill, self.group, 2, draws), **f64) if self.gen is not None else None)
+            self._ucur.append(self._refill)
+            self._call.append([((ops.dtype_code(dtype), n, vp(slot.outs[m].data_ptr()), draws),
+                                (vp(r[0].data_ptr()), vp(r[1].data_ptr()), vp(r[2].data_ptr()),
+                                 vp(st[m].data_ptr()), len(self.axis_qubit), self._axes),
+                                (vp(r[3].data_ptr()), wsb, vp(slot.stream.cuda_stream)))
+                               for m in range(self.group)])
+        self._mws = torch.empty(_lib.TQ_BORN_POOL_MERGE_WORKSPACE, dtype=torch.uint8, device=self.device)
+        self._merged = torch.cuda.Event()
+        # one validated call per member (arguments, buffers, the kernels' code objects) on a block of
+        # zeros, which contributes nothing: the pools stay empty
+        zu = torch.zeros(draws, **f64)
+        for s, slot in enumerate(self.slots):
+            with torch.cuda.stream(slot.stream):
+                r = self.rbuf[s]
+                for m in range(self.group):
+                    slot.outs[m].zero_()
+                    ops.born_pool_sample(slot.outs[m], zu, zu, r[0], r[1], r[2], axis_qubit=self.axis_qubit,
+                                         base=self.base[0], stats=self.sstat[s][m], workspace=r[3])
+        torch.cuda.synchronize(self.device)
+
+    def _launch(self, slot: _Slot) -> None:
+        rows = list(slot.pending)
+        if not rows:
+            return
+        super()._launch(slot)
+        s = self.slots.index(slot)
+        row = 2 * self.draws * 8
+        if self.gen is not None:
+            if self._ucur[s] == self._refill:
+                with torch.cuda.stream(slot.stream):
+                    self.ubuf[s].uniform_(0.0, 1.0, generator=self.gen)
+                self._ucur[s] = 0
+            u0 = self.ubuf[s].data_ptr() + self._ucur[s] * self.group * row
+            self._ucur[s] += 1
+        else:
+            u0 = self.uniforms.data_ptr()
+        for m, r in enumerate(rows):
+            head, outs, tail = self._call[s][m]
+            up = u0 + (m if self.gen is not None else r) * row
+            check(self._fn(*head, ctypes.c_void_p(up), ctypes.c_void_p(up + self.draws * 8), *outs,
+                           self.base[r], *tail), "tq_born_pool_sample")
+        slot.event.record(slot.stream)
+
+    def step(self) -> None:
+        """Enqueue the next block (as `BlockPipeline.step()`).  Returns None: a block leaves no
+        result of its own, only its share of the slot's reservoir; see `result()`."""
+        if self._closed:
+            raise RuntimeError("the sampler is closed")
+        super().step()
+
+    def result(self, merge_uniforms: Optional[torch.Tensor] = None):
+        """Flush, make the current stream wait for every slot, and merge the slots' reservoirs in
+        slot order 0, 1, ... into a fresh output: device tensors `(words, prob, pool)` -- `draws`
+        int64 bitstring words (bit q = qubit q), their float64 probabilities |amplitude|^2, and
+        `pool` = (the mass of every block stepped so far, the sum of |amplitude|^4, the number of
+        blocks that contributed, the slots taken from the last slot merged).  With no mass at all
+        the words are -1 and the probabilities 0.  Row s of `merge_uniforms` (`(inflight, draws)`
+        float64, device) decides what is taken from slot s; without it the rows come from the
+        generator (one seeded with `seed` when the blocks' uniforms were given).  The slot reservoirs stay intact: stepping may go on, and a later `result()`
+        reflects more blocks."""
+        if self._closed:
+            raise RuntimeError("the sampler is closed")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        if merge_uniforms is None:
+            if self.gen is None and self._mgen is None:   # the blocks' uniforms were given: `seed` serves the merges
+                self._mgen = torch.Generator(self.device)
+                self._mgen.manual_seed(self._seed)
+            mv = torch.rand((self.inflight, self.draws), generator=self.gen or self._mgen, **f64)
+        else:
+            mv = merge_uniforms
+            if (not isinstance(mv, torch.Tensor) or mv.dtype != torch.float64 or mv.device != self.device
+                    or tuple(mv.shape) != (self.inflight, self.draws) or not mv.is_contiguous()):
+                raise ValueError(f"merge_uniforms must be a contiguous ({self.inflight}, {self.draws}) float64 tensor on {self.device}")
+        self.wait()
+        cur = torch.cuda.current_stream(self.device)
+        words = torch.full((self.draws,), -1, dtype=torch.int64, device=self.device)
+        prob = torch.zeros(self.draws, **f64)
+        pool = torch.zeros(4, **f64)
+        for s in range(self.inflight):
+            r = self.rbuf[s]
+            ops.born_pool_merge(words, prob, pool, r[0], r[1], r[2], mv[s], workspace=self._mws)
+        # the slots' next launches overwrite what these merges read
+        self._merged.record(cur)
+        for slot in self.slots:
+            if slot.stream is not cur:
+                slot.stream.wait_event(self._merged)
+        return words, prob, pool
+
+    def reset(self) -> None:
+        """Flush, start again at block 0 and empty every slot's reservoir."""
+        super().reset()
+        for s, slot in enumerate(self.slots):
+            with torch.cuda.stream(slot.stream):
+                self.rbuf[s][2].zero_()
+
+    def run(self, n: Optional[int] = None, merge_uniforms: Optional[torch.Tensor] = None):
+        """Step through the next `n` blocks (default: every block once) and return host copies of
+        `result(merge_uniforms)`."""
+        n = len(self.blocks) if n is None else n
+        for _ in range(n):
+            self.step()
+        return tuple(t.cpu() for t in self.result(merge_uniforms))
+
+    def close(self) -> None:
+        """Release the pipeline's private plans and the sampler's buffers now."""
+        super().close()
+        self.rbuf, self.sstat, self.ubuf, self._call = [], [], [], []
+        self.uniforms = None
