@@ -176,7 +176,10 @@ int tq_plan_clone(tq_plan src, tq_plan* out);
  * "s2_programs" = 1 (default, env TQ_S2_PROG) runs the sweep2 register-block passes whose gate
  * sequence is in the kernel's program set as straight-line pass programs, 0 all of them on the
  * per-gate interpreter (no recompile; queries "n_s2_prog_gate_work" / "n_s2_block_gate_work":
- * gate work under programs / of all block passes, "n_s2_prog_passes_<id>", "n_s2_programs");
+ * gate work under programs / of all block passes, "n_s2_prog_passes_<id>", "n_s2_programs";
+ * "tables_digest" / "whole_tables_digest": FNV-1a-64, masked to 63 bits, over every gather table,
+ * every descriptor blob as it stands and, per op, what the executor forms its launch from: equal
+ * between two builds of the library whose planners agree);
  * "fold_slices" = 1 (default, env TQ_FOLD_SLICES): a plan with sliced modes also holds the same
  * network compiled with no sliced modes (the whole program), and an execute call over every
  * slice (begin 0, end n_slices, step 1) runs that instead of the slice lanes when it moves no

@@ -429,6 +429,7 @@ int64_t tq_plan_query(tq_plan p, const char* key) {
   if (k.rfind("n_s2_prog_passes_", 0) == 0) return tq::plan_s2_prog_passes(P, atoi(k.c_str() + 17));
   if (k == "n_s2_block_gate_work") return tq::plan_s2_gate_work(P, false);
   if (k == "n_s2_prog_gate_work") return tq::plan_s2_gate_work(P, true);
+  if (k == "tables_digest") return tq::plan_tables_digest(P);
   if (k == "out_numel") return P.out_numel;
   // the whole program (Plan::whole): will a call over every slice run it; its costs; calls it ran
   if (k == "fold_slices") return tq::plan_folds(P, 0, P.n_slices, 1) ? 1 : 0;
@@ -447,6 +448,7 @@ int64_t tq_plan_query(tq_plan p, const char* key) {
     if (const int64_t v = frozen_query(W, P.use_seq, false, k.substr(6)); v != -2) return v;
     if (k == "whole_n_s2_block_gate_work") return tq::plan_s2_gate_work(W, false);
     if (k == "whole_n_s2_prog_gate_work") return tq::plan_s2_gate_work(W, true);
+    if (k == "whole_tables_digest") return tq::plan_tables_digest(W);
   }
   return -1;
 }

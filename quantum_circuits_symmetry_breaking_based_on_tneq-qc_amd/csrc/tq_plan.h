@@ -1,5 +1,6 @@
 // Contraction-plan compiler and executor (host C++ over the HIP kernels): the Plan and the
-// functions tq_capi.cpp calls.  Implemented in tq_plan.cpp (compiler), tq_plan_exec.cpp (executor) and
+// functions tq_capi.cpp calls.  Implemented in tq_plan.cpp (lowering), tq_sweep2_layout.cpp (sweep-chain
+// layouts), tq_plan_finish.cpp (finishing a lowered plan), tq_plan_exec.cpp (executor) and
 // tq_plan_run.cpp (materialize / release, graph cache, run); tq_plan_internal.h: what those share.
 #pragma once
 #include <cstdint>
@@ -326,6 +327,10 @@ void plan_s2_programs(Plan& P, bool on);
 int64_t plan_s2_gate_work(const Plan& P, bool programs_only);
 // register-block passes (of every sweep2 descriptor, one-chunk forms included) that run program id
 int64_t plan_s2_prog_passes(const Plan& P, int id);
+// FNV-1a-64 (masked to 63 bits) over what the device reads of a compiled program: every gather
+// table, every descriptor blob as it stands (program ids included), and per op, field by field,
+// what the executor forms its launch from.  Two builds whose planners agree give the same value
+int64_t plan_tables_digest(const Plan& P);
 // a copy of a compiled plan without any device state (arena, tables, graphs, events): the
 // same schedule for another stream / block (tq_plan_clone)
 void plan_clone_compiled(const Plan& src, Plan& dst);

@@ -1,8 +1,14 @@
 // What the plan sources share behind tq_plan.h (the interface tq_capi.cpp sees):
-//   tq_plan.cpp       the plan compiler (class Compiler, plan_compile and the compile-time plan
-//                     functions)
-//   tq_plan_exec.cpp  Exec: one plan's (or a lockstep group's) launch sequence on a stream
-//   tq_plan_run.cpp   materialize / release, the hipGraph cache, plan_run, plan_run_group
+//   tq_plan.cpp            the plan compiler's lowering (class Compiler, plan_compile and the
+//                          compile-time plan functions)
+//   tq_sweep2_layout.cpp   the sweep-chain layout planner (chain_shape, s2_layout, s2_blob, ...) and
+//                          the inspectors of a plan's sweep2 descriptors; the layout functions see
+//                          neither the Plan nor the Compiler
+//   tq_plan_finish.cpp     plan_finish: arena / lane layout, assign_amax, tables, build_schedule,
+//                          the describe text; plan_planes_layout, plan_tables_digest
+//   tq_plan_compile.h      the compile-time types those three share (Live, Chain, ChainShape, ...)
+//   tq_plan_exec.cpp       Exec: one plan's (or a lockstep group's) launch sequence on a stream
+//   tq_plan_run.cpp        materialize / release, the hipGraph cache, plan_run, plan_run_group
 #pragma once
 #include "tq_env.h"
 #include "tq_plan.h"

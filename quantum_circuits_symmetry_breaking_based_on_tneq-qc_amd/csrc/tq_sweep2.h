@@ -27,7 +27,7 @@ constexpr int kS2ChunkBytes = 65536;   // LDS tile per workgroup
 constexpr int kS2MaxChunkBits = 13;    // log2(chunk elements) for 8-byte elements
 constexpr int kS2MaxColBits = 48;
 constexpr int kS2LogThreads = 9;       // 512 threads per workgroup
-// Pass barriers (kS2PmSync, planned in tq_plan.cpp s2_layout): thread t takes the groups
+// Pass barriers (kS2PmSync, planned in tq_sweep2_layout.cpp fill_sync): thread t takes the groups
 // gi == t (mod 2^kS2LogThreads) of every pass, so the 64-lane wave w owns exactly the groups whose
 // gi bits [kS2WaveBits, kS2LogThreads) equal w.  The kernel asserts both constants.
 constexpr int kS2WaveBits = 6;         // log2(wave size): CDNA waves are 64 lanes
@@ -106,7 +106,7 @@ struct S2Desc {
   int32_t ld_hc[kS2MaxSlots] = {}, st_hc[kS2MaxSlots] = {};
   int32_t vsw[12] = {};          // swizzle vector of each position (kS2MaxPos used)
   // modeled extra LDS bank-conflict cycles / conflict-free cycles of a chunk: the r04 column-only
-  // swizzle, the chosen one (tq_plan.cpp s2_layout)
+  // swizzle, the chosen one (tq_sweep2_layout.cpp choose_swizzle)
   float lds_model[2] = {};
   int32_t nsync = 0;             // passes preceded by a workgroup barrier (kS2PmSync)
   // byte offsets (in the plan's descriptor blob) of the host-built lane / chunk-base tables
@@ -215,7 +215,7 @@ struct S2Op {
   // ((h_re, h_im | l_re, l_im) in the element's 8 bytes; the consuming GEMM's SplitPre); amax
   // still tracks the unscaled values
   const int32_t* split_sc = nullptr;
-  // host-built tables behind the descriptor (tq_plan.cpp s2_blob; nullptr = computed in the
+  // host-built tables behind the descriptor (tq_sweep2_layout.cpp s2_blob; nullptr = computed in the
   // kernel): per thread (byte offset of its load / store element, LDS address of both), and per
   // chunk (memory base of its load / store elements) -- S2Desc::aux_lanes / aux_cb
   const uint4* lanes = nullptr;

@@ -5,7 +5,7 @@
 // opt_einsum pairwise step at einsum_strategy.py:639-643 absorbs one (2,2,2,2) gate, or a
 // gate with an input state / output projector folded in, into a running tensor) are long
 // chains of steps that each touch a few legs.  For chains whose modes all have power-of-two
-// extents the plan compiler (tq_plan.cpp) gives every mode bit of the working set a fixed
+// extents the plan compiler (tq_sweep2_layout.cpp) gives every mode bit of the working set a fixed
 // position bit of a tile index; a gate with K inputs and N outputs then works on disjoint
 // groups (one assignment of the positions it does not touch): read K tile elements, write N —
 // outputs take the positions the gate frees, so the tile is updated in place and every gate
@@ -686,7 +686,7 @@ __global__ void __launch_bounds__(NT, SEQ ? 1 : 4) sweep2_kernel(S2Launch L) {
     continue;
   const S2Op& op = L.op[j];
   const S2Desc* __restrict__ d = op.desc;
-  // host-built per-thread lane offsets and per-chunk bases (S2Op::lanes / cbase, tq_plan.cpp
+  // host-built per-thread lane offsets and per-chunk bases (S2Op::lanes / cbase, tq_sweep2_layout.cpp
   // s2_blob): loaded from memory together with the descriptor staging below -- no LDS table walk
   // (and no barrier) between the descriptor and the first chunk's loads
   const bool host_lanes = op.lanes != nullptr, host_cb = op.cbase != nullptr;
@@ -978,7 +978,7 @@ __global__ void __launch_bounds__(NT, SEQ ? 1 : 4) sweep2_kernel(S2Launch L) {
       PassHead cur;
       read_head(p, cur);
       // the workgroup barrier before a pass only where another wave may own its elements
-      // (kS2PmSync, tq_plan.cpp s2_layout); otherwise every element this pass touches was
+      // (kS2PmSync, tq_sweep2_layout.cpp fill_sync); otherwise every element this pass touches was
       // last touched by this wave, whose LDS accesses complete in order
       if (p > 0 && (cur.w[kS2PmCount] & kS2PmSync)) __syncthreads();
       asm volatile("" ::: "memory");

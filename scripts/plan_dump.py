@@ -62,6 +62,9 @@ def main() -> None:
         print(f"n_s2_prog_passes_{i} = {plan.query(f'n_s2_prog_passes_{i}')}")
     for key in WHOLE_KEYS:
         print(f"{key} = {plan.query(key)}")
+    # what the device reads (gather tables, descriptor blobs, launch fields), after the older keys
+    for key in ("tables_digest", "whole_tables_digest"):
+        print(f"{key} = {plan.query(key)}")
 
 
 if __name__ == "__main__":

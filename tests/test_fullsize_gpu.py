@@ -61,7 +61,7 @@ def test_c2_single_amplitude_vs_oracle(dev):
 @pytest.mark.parametrize("cfg", ["C3", "C4"])
 def test_chain_launch_equals_one_launch_per_level(dev, cfg):
     """Consecutive small hoisted sweep2 levels run as ONE chain launch by default (a workgroup
-    per stream, one-chunk layouts, LDS hand-offs between the ops of a stream: tq_plan.cpp
+    per stream, one-chunk layouts, LDS hand-offs between the ops of a stream: tq_plan_finish.cpp
     Plan::seq_once, S2Launch::seq) -- C3's and C4's first levels; the same plan with
     "sweep_chain" = 0 launches them level by level (multi-chunk layouts).  The per-element
     arithmetic is the same gate sequence, so the two agree to rounding; a replay is exact.
@@ -85,7 +85,7 @@ def test_chain_launch_equals_one_launch_per_level(dev, cfg):
 def test_cooperative_chain_equals_one_launch_per_level(dev):
     """C2's 26 levels of one multi-chunk sweep2 op run as ONE cooperative launch with
     "sweep_coop" = 1 (8 workgroups; complex128: 32 + 2 ops), each op's chunks spread over them, a counter barrier between the ops, sc1 loads /
-    stores: tq_plan.cpp Plan::coop_once, S2Launch::sync); "sweep_coop" = 0 (the default, measured
+    stores: tq_plan_finish.cpp Plan::coop_once, S2Launch::sync); "sweep_coop" = 0 (the default, measured
     faster) launches them level by level.  Same descriptors, same arithmetic: the results are bit-identical, on every one of many
     graph replays (a missed barrier shows up as a stale chunk), eager and captured, and no wait
     gave up."""

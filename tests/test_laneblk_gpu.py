@@ -1,4 +1,4 @@
-"""Lane blocks (TQ_S2_LANEBLK=1, tq_plan.cpp lane_span / tq_sweep2.hip blk_swap): register blocks of
+"""Lane blocks (TQ_S2_LANEBLK=1, tq_sweep2_layout.cpp lane_span / tq_sweep2.hip blk_swap): register blocks of
 6 positions, 4 in a thread's registers and 2 on its lane bits 4 / 5, with v_permlane16 / 32_swap
 trading positions between them.  Off by default (the same speed); this checks the
 opt-in path end to end on the headline network: a C4 block with lane blocks active against the

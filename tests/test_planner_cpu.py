@@ -98,7 +98,7 @@ def test_native_plan_c4_structure():
 
 def test_c4_gemm_operand_max_comes_from_its_producers():
     """The C4 boundary GEMM (complex64, K-outer fast path) reads both operands' max |x| from the
-    per-slice sweep ops that store them (csrc/tq_plan.cpp assign_amax), not from a pre-pass."""
+    per-slice sweep ops that store them (csrc/tq_plan_finish.cpp assign_amax), not from a pre-pass."""
     import re
     e, p = _plan(config_task("C4g"))
     d = p.describe().splitlines()
@@ -149,7 +149,7 @@ def test_launch_schedule_covers_every_op_once_and_batches_sweeps():
 
 def test_sweep_tiles_keep_32_columns_on_large_tensors():
     """Tiles with more than 2^(13-5) positions (fewer than 32 columns per chunk) are reserved for
-    tensors of at most 2^22 elements (SWEEP2 layout rule, csrc/tq_plan.cpp s2_layout)."""
+    tensors of at most 2^22 elements (SWEEP2 layout rule, csrc/tq_sweep2_layout.cpp choose_columns)."""
     import re
     e, p = _plan(config_task("C4g"))
     n_wide = 0
@@ -219,7 +219,7 @@ def test_sweep2_lane_offsets_stay_32bit(n_legs, want_s2):
 def test_boundary_gemm_takes_presplit_operands(cfg):
     """The boundary GEMM of C3 / C4 is a pre-split candidate: both operands come from per-slice
     sweep2 ops that nothing else reads, so those ops may store the f16 terms the GEMM consumes
-    (tq_plan.cpp Compiler::assign_amax); the operand-max words stay in place for the check."""
+    (tq_plan_finish.cpp assign_amax); the operand-max words stay in place for the check."""
     e, p = _plan(config_task(cfg))
     gemm = [l for l in p.describe().splitlines() if " GEMM " in l]
     assert len(gemm) == 1 and "amax<-" in gemm[0]
@@ -238,7 +238,7 @@ def test_boundary_gemm_takes_presplit_operands(cfg):
 def test_slice_lanes_within_the_arena_budget():
     """Slices run in batches of `lanes` (a power of two) within an arena budget (C3: 64
     latency-bound slices, 32 per batch, each lane with its own copy of the per-slice buffers);
-    C4's 1.1-GiB per-slice part gets 4 (the lane copies stay within 6 GiB; tq_plan.cpp, Plan::lanes)."""
+    C4's 1.1-GiB per-slice part gets 4 (the lane copies stay within 6 GiB; tq_plan_finish.cpp, Plan::lanes)."""
     e3, p3 = _plan(config_task("C3"))
     assert p3.query("lanes") == 32
     e4, p4 = _plan(config_task("C4g"))
@@ -250,7 +250,7 @@ def test_slice_lanes_within_the_arena_budget():
 def test_small_hoisted_levels_run_as_one_chain_launch():
     """Consecutive hoisted levels of small sweep2 ops (the whole tensor fits one 64-KiB tile and
     the default layout has at most 2 chunks) run as one chain launch, a workgroup per stream
-    (tq_plan.cpp Plan::seq_once): the first levels of C2, C3 and C4 (C3 / C4: the left and right
+    (tq_plan_finish.cpp Plan::seq_once): the first levels of C2, C3 and C4 (C3 / C4: the left and right
     halves on streams of their own); consecutive ops of a stream hand their tensor over in LDS.
     C2's later 4-chunk levels stay one launch each (measured faster, tq_plan.cpp
     s2_seq_max_chunks); "sweep_chain" = 0 restores one launch per level."""
@@ -271,7 +271,7 @@ def test_small_hoisted_levels_run_as_one_chain_launch():
 def test_multi_chunk_hoisted_levels_run_as_one_cooperative_launch():
     """C2's hoisted levels of one multi-chunk sweep2 op each (after its one-chunk chain) form
     ONE cooperative launch of 8 workgroups (its most common chunk count) with a counter barrier
-    between the ops (tq_plan.cpp Plan::coop_once), run when "sweep_coop" = 1 (measured slower,
+    between the ops (tq_plan_finish.cpp Plan::coop_once), run when "sweep_coop" = 1 (measured slower,
     so off by default: one launch per level).  C3 / C4 have no such run (their multi-chunk levels
     hold several ops or are per slice)."""
     e, p = _plan(config_task("C2"))
@@ -294,7 +294,7 @@ def test_multi_chunk_hoisted_levels_run_as_one_cooperative_launch():
 def test_lane_batched_boundary_gemm_and_lane_sum(cfg):
     """With slice lanes the boundary GEMM (lane-local operands) is one batched launch per batch
     (`lanes`), and since only the output permute reads its result the lanes' results are summed
-    before that permute runs once (`lane-sum`; tq_plan.cpp Op::lane_batch / lane_sum)."""
+    before that permute runs once (`lane-sum`; tq_plan_finish.cpp Op::lane_batch / lane_sum)."""
     e, p = _plan(config_task(cfg))
     d = p.describe().splitlines()
     gemm = [l for l in d if " GEMM " in l]

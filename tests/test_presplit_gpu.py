@@ -1,5 +1,5 @@
 """Pre-split boundary-GEMM operands on the GPU (opt-in path) (tq_gemm.hip SplitPre, tq_sweep2.hip f16_terms,
-tq_plan.cpp Op::ps_cand): the per-slice sweep ops that store the two operands of the C3 / C4g
+tq_plan_finish.cpp Op::ps_cand): the per-slice sweep ops that store the two operands of the C3 / C4g
 boundary GEMM write them as the f16 terms (h, l) of their values scaled by 2^sc, sc predicted
 from the previous slice's operand max; the GEMM checks the true max against the window
 (max * 2^sc in [2^0, 2^15)) and a slice outside it is re-run on the split path.

@@ -1,4 +1,4 @@
-"""The sweep2 compiler's gate re-listing (tq_plan.cpp s2_reorder_squares, TQ_S2_REORDER): commuting
+"""The sweep2 compiler's gate re-listing (tq_sweep2_layout.cpp s2_reorder_squares, TQ_S2_REORDER): commuting
 square gates are re-listed into fuller register blocks only when that saves passes, so every op
 keeps or lowers its pass count, and the plan's other ops stay as they were.  Compile-only (no GPU):
 the flag is read once per process, so each setting compiles in a child process.  Parity of the
@@ -68,7 +68,7 @@ print(json.dumps({"passes": sum(int(l.split("passes=")[1].split()[0]) for l in s
 
 @pytest.mark.timeout(600)
 def test_lane_blocks_are_opt_in_and_cut_passes():
-    """TQ_S2_LANEBLK=1 (lane blocks: 6-position register blocks over 4 lanes, tq_plan.cpp
+    """TQ_S2_LANEBLK=1 (lane blocks: 6-position register blocks over 4 lanes, tq_sweep2_layout.cpp
     lane_span) compiles C4 with lane passes and fewer passes than the default, which has none
     (r06: C4's big sweep ops 174 -> 125 passes).  Parity of the opt-in path: test_laneblk_gpu.py."""
     import json

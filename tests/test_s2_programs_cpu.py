@@ -1,4 +1,4 @@
-"""Pass programs of the sweep2 register-block passes (tq_sweep2.h kS2Progs, tq_plan.cpp
+"""Pass programs of the sweep2 register-block passes (tq_sweep2.h kS2Progs, tq_sweep2_layout.cpp
 plan_s2_programs): the planner marks every plain block pass whose block-local gate sequence is in
 the program set (up to the order of commuting gates) with a program id, which the kernel runs as
 straight-line code instead of its per-gate interpreter.  Compile-only (no GPU): coverage of the

@@ -1,4 +1,4 @@
-"""The sweep2 pass-barrier elision (kS2PmSync, tq_plan.cpp s2_layout: no workgroup barrier between
+"""The sweep2 pass-barrier elision (kS2PmSync, tq_sweep2_layout.cpp fill_sync: no workgroup barrier between
 two passes whose elements stay with the same waves) must not change a single bit: the same plans
 compiled with TQ_S2_WAVELOCAL=0 (a barrier before every pass) in a child process give bitwise the
 same amplitudes on multi-pass layouts (C2: 33 dependent levels; a C4-form network with deferred
